@@ -15,10 +15,33 @@ sync on both sides, MAX time over ranks, rank 0 prints ONE JSON line.
 per-shard streams sharded across ranks — weak scaling, no
 data-path collective (the cross-shard repartition exchange is config #4,
 a later row).
+
+A plain run does only what the headline needs: generate + upload the stream,
+warm up, time the K steps, print the line. `--full` adds the side reports
+that take runs of their own: the staging-inclusive `h2d_staged` leg, the
+`drain_host` leg, and the CPU-oracle `cpu_baseline` / `gpu_vs_cpu` ratio.
+
+`--dump-outputs DIR` writes what the timed path left behind as float64
+`DIR/<name>.npy` (rank r > 0 writes `<name>_rank<r>.npy`); inputs are seeded,
+so two builds run with the same arguments can be compared array for array:
+  shard_latest_seq      [nshards]  per-shard seq after the last timed step
+  shard_apply_failures  [nshards]  per-shard device-detected apply failures
+  apply_stats           [5]        ticks, updates, records, blob bytes and
+                                   payload bytes the timed ticks reported
+                                   (records/payload are device-computed)
+  last_step_checksum    [nshards, 2]  (headline path only) hi/lo 32-bit halves
+                                   of each shard's full-content checksum
+                                   after the LAST timed step's window. The
+                                   timed store is a ring whose bytes recycle
+                                   (reads over it are undefined by contract),
+                                   so that window is re-applied through the
+                                   same tick path into a retaining store on a
+                                   second engine and checksummed there.
 """
 import argparse
 import ctypes as C
 import json
+import mmap
 import os
 import sys
 import time
@@ -43,7 +66,14 @@ def parse_args():
     p.add_argument("--tick-updates", type=int, default=819200)
     p.add_argument("--max-ticks-resident", type=int, default=6,
                    help="distinct ticks of data generated/uploaded; steps cycle over them")
-    p.add_argument("--cpu-baseline", action="store_true", default=True)
+    p.add_argument("--full", action="store_true",
+                   help="also run the side reports that take runs of their "
+                        "own (h2d_staged, drain_host, cpu_baseline legs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the timed path's "
+                        "outputs as DIR/<name>.npy (float64)")
+    p.add_argument("--cpu-baseline", action="store_true", default=True,
+                   help="(with --full) time the CPU oracle applier")
     p.add_argument("--no-cpu-baseline", dest="cpu_baseline", action="store_false")
     p.add_argument("--cpu-sample-seconds", type=float, default=10.0)
     p.add_argument("--traffic-file", default=os.path.join(REPO, "profiles", "traffic.json"),
@@ -51,7 +81,7 @@ def parse_args():
     p.add_argument("--h2d", action="store_true",
                    help="measure the PCIe-inclusive staging path instead (side report)")
     p.add_argument("--no-legs", action="store_true",
-                   help="skip the h2d/drain side legs (clean-profile runs)")
+                   help="(with --full) skip the h2d/drain side legs")
     p.add_argument("--device-wrap", action="store_true",
                    help="TESTING ONLY: map rank devices modulo the visible "
                         "GPU count so a multi-rank run can be validated on "
@@ -215,6 +245,65 @@ def cpu_baseline_leg(raw_arena, used, descs, n, nshards, target_s, snappy=False)
     return out
 
 
+def last_window_checksums(arena, descs, first, n, nshards, device):
+    """Re-apply descs [first, first+n) — the last timed step's window — with
+    one tick into a retaining (non-ring) store on a second engine and return
+    each shard's content checksum as [nshards, 2] float64 (hi, lo 32 bits)."""
+    import numpy as np
+
+    dt = np.dtype([("shard", "<u4"), ("len", "<u4"), ("off", "<u8"), ("ts", "<i8")])
+    assert dt.itemsize == C.sizeof(ra.ffi.GraUpdateDesc)
+    win = np.frombuffer(descs, dtype=dt)[first:first + n].copy()
+    base = int(win["off"][0])
+    end = int(win["off"][-1]) + int(win["len"][-1])
+    win["off"] -= base
+    wdescs = (ra.ffi.GraUpdateDesc * n).from_buffer(win)
+    warena = (C.c_uint8 * (end - base)).from_buffer(arena, base)
+    eng = ra.Engine(nshards=nshards, device=device,
+                    store_bytes=int((end - base) * 1.3) + (1 << 30))
+    try:
+        rep = eng.upload(C.cast(warena, C.POINTER(C.c_uint8)), end - base,
+                         wdescs, n)
+        rep.tick(0, n)
+        rep.sync()
+        out = np.empty((nshards, 2), dtype=np.float64)
+        for s in range(nshards):
+            db = eng.open(s)
+            cs = db.checksum()
+            db.close()
+            out[s] = (cs >> 32, cs & 0xFFFFFFFF)
+        del rep
+    finally:
+        eng.close()
+    return out
+
+
+def dump_outputs(outdir, eng, st, nshards, rank, extra=None):
+    """Write the timed engine's per-shard results and tick stats (plus any
+    `extra` arrays) as float64 .npy files under outdir."""
+    import numpy as np
+
+    seqs = np.empty(nshards, dtype=np.float64)
+    fails = np.empty(nshards, dtype=np.float64)
+    for s in range(nshards):
+        db = eng.open(s)
+        seqs[s] = db.latest_seq()
+        fails[s] = db.counters()["apply_failures"]
+        db.close()
+    arrays = {
+        "shard_latest_seq": seqs,
+        "shard_apply_failures": fails,
+        "apply_stats": np.array([st.ticks, st.updates, st.records,
+                                 st.blob_bytes, st.payload_bytes],
+                                dtype=np.float64),
+    }
+    arrays.update(extra or {})
+    os.makedirs(outdir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a)
+
+
 def run_repartition(args, rank, world, local, dist):
     """Config #4 path: per timed step, an all-to-all re-homes one tick of
     update blobs to their owner ranks over RCCL/xGMI, then the owner applies
@@ -327,6 +416,8 @@ def main():
             # RCCL-all-to-all + zero-copy apply path.
             "secondary": True,
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng, st, args.nshards, rank)
         if rank == 0:
             print(json.dumps(result))
         eng.close()
@@ -338,7 +429,9 @@ def main():
     n_ticks_data = min(args.warmup + args.steps, args.max_ticks_resident)
     n_upd = args.tick_updates * n_ticks_data
     worst = n_upd * (23 + args.key_len + args.val_len + 16) + 4096
-    arena = (C.c_uint8 * worst)()
+    # anonymous mapping: pages are touched once, by the generator (a plain
+    # ctypes array would zero-fill all ~5 GB first)
+    arena = (C.c_uint8 * worst).from_buffer(mmap.mmap(-1, worst))
     arena_p = C.cast(arena, C.POINTER(C.c_uint8))
     descs = (ra.ffi.GraUpdateDesc * n_upd)()
     g = ra.ffi.GraGenOpts(args.nshards, args.key_len, args.val_len, args.kind,
@@ -501,16 +594,25 @@ def main():
                       "records": st.records},
     }
 
-    if (rank == 0 and world == 1 and not args.h2d and not args.snappy
-            and not args.no_legs):
-        # staging-inclusive side line on every headline run
+    if args.dump_outputs:
+        extra = None
+        if not args.h2d and not args.snappy:
+            last = args.warmup + args.steps - 1
+            extra = {"last_step_checksum": last_window_checksums(
+                arena, descs, (last % n_ticks_data) * args.tick_updates,
+                args.tick_updates, args.nshards, local)}
+        dump_outputs(args.dump_outputs, eng, st, args.nshards, rank, extra)
+
+    if (args.full and rank == 0 and world == 1 and not args.h2d
+            and not args.snappy and not args.no_legs):
+        # staging-inclusive side line on every --full run
         result["h2d_staged"] = h2d_side_leg(eng, arena, used, descs, n_upd, args)
         # host-drain side line; separate engine so the
         # drain mode never touches the headline engine's state
         result["drain_host"] = drain_side_leg(
             C.cast(arena, C.POINTER(C.c_uint8)), descs, n_upd, args)
 
-    if rank == 0 and world == 1 and args.cpu_baseline:  # contract: N=1 only
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline:  # N=1 only
         if args.snappy:
             result["cpu_baseline"] = cpu_baseline_leg(
                 comp, comp_used.value, cdescs, n_upd, args.nshards,
