@@ -487,7 +487,7 @@ __global__ void k_multiget(const uint8_t *__restrict__ store,
                            const uint8_t *__restrict__ keybuf, uint32_t nq,
                            uint8_t *__restrict__ valbuf, uint32_t val_stride,
                            GraGetResult *__restrict__ out,
-                           MgExtra *__restrict__ extra, int use_kpref) {
+                           MgExtra *__restrict__ extra) {
   __shared__ uint64_t sh_term_seq[256];
   __shared__ uint64_t sh_term_ref[256]; /* (run<<32)|entry, ~0 = none */
   __shared__ uint64_t sh_merge_seq[256];
@@ -505,7 +505,7 @@ __global__ void k_multiget(const uint8_t *__restrict__ store,
     for (uint32_t i = threadIdx.x; i < rv.n_entries; i += blockDim.x) {
       wb::RecHdr h = hdrs[i];
       if (h.type != wb::kRangeDeletion &&
-          (h.key_len != klen || (use_kpref && h.kpref != qpref)))
+          (h.key_len != klen || h.kpref != qpref))
         continue; /* header-only reject: no payload touch */
       uint32_t rel = h.kv_off - rv.pay_rel_base;
       if (h.type == wb::kRangeDeletion) {
@@ -829,11 +829,15 @@ __global__ void k_checksum(const uint8_t *__restrict__ store,
     atomicAdd(out, (unsigned long long)local);
 }
 
+/* Diagnostic switches read "1" as on; callers latch the result in a
+ * function-local static, so each variable is read once per process. */
+static bool env_flag(const char *name) {
+  const char *v = getenv(name);
+  return v && v[0] == '1';
+}
+
 static bool gra_check_staging() {
-  static const bool on = [] {
-    const char *v = getenv("GRA_CHECK_STAGING");
-    return v && v[0] == '1';
-  }();
+  static const bool on = env_flag("GRA_CHECK_STAGING");
   return on;
 }
 
@@ -846,18 +850,63 @@ struct Stats {
 };
 
 constexpr int kSlots = 8;
-constexpr int kEventsPerTick = 12; /* 10 = decode start (prep stream),
-                                      11 = decode done */
+/* One entry per point a tick may record. The h2d and snappy legs run on their
+ * own streams and are timed start->done; the rest chain along the main
+ * stream. Which ones a tick recorded is in TickRec::evmask. */
+enum TickEvent {
+  kEvTickStart,
+  kEvH2dStart,    /* h2d stream */
+  kEvH2dDone,     /* h2d stream; main gates on it */
+  kEvSnappyStart, /* prep stream */
+  kEvSnappyDone,  /* prep stream; main gates on it */
+  kEvAfterDecode, /* GRA_DETAILED_EVENTS only */
+  kEvAfterScan,   /* GRA_DETAILED_EVENTS only */
+  kEvAfterEmit,
+  kEvAfterCopy,
+  kEvMainEnd,     /* after k_rundesc */
+  kEvPublished,   /* copyout stream: run descriptors are on the host */
+  kEventsPerTick
+};
 
 struct TickRec {
   int slot = -1;
   uint32_t n = 0, ngroups = 0;
   uint64_t blob_bytes = 0;
-  bool h2d_timed = false;
-  uint32_t evmask = 0; /* which ev[i] were recorded this tick */
+  uint32_t evmask = 0; /* which events were recorded this tick */
   std::vector<uint32_t> counts; /* per-update record counts (error recovery) */
   std::shared_ptr<uint8_t> drain_buf; /* drain-host: this tick's pinned arena */
   hipEvent_t ev[kEventsPerTick];
+
+  hipError_t record(TickEvent k, hipStream_t s) {
+    evmask |= bit(k);
+    return hipEventRecord(ev[k], s);
+  }
+  bool has(TickEvent k) const { return evmask & bit(k); }
+  static uint32_t bit(TickEvent k) { return 1u << k; }
+};
+
+/* What enqueue_tick applies. Exactly one blob source is set:
+ *  - resident: d_blobs + d_descs already on the device (gra_replay_tick;
+ *    with the snappy pre-stage, d_blobs is the arena k_snappy fills first);
+ *  - staged: stage_src/stage_bytes are copied into the engine's staging
+ *    buffer for this tick, with the descs either uploaded from h_descs
+ *    (streaming) or already device-cached in d_descs, rebased to the staged
+ *    window (gra_replay_tick_h2d). */
+struct TickInput {
+  uint32_t n = 0;
+  const std::vector<GroupDesc> *groups = nullptr; /* always copied to the slot */
+  const GroupDesc *d_groups = nullptr; /* optional device-cached copy */
+  uint64_t blob_bytes = 0;
+  std::vector<uint32_t> counts; /* moved into the tick */
+  const uint8_t *d_blobs = nullptr;
+  const UpdDesc *d_descs = nullptr;
+  const void *stage_src = nullptr;
+  size_t stage_bytes = 0;
+  const UpdDesc *h_descs = nullptr;
+  /* snappy pre-stage (resident source only) */
+  const uint8_t *d_comp = nullptr;
+  const SnapTask *d_snaptasks = nullptr;
+  hipEvent_t window_ev = nullptr;
 };
 
 struct Slot {
@@ -906,16 +955,15 @@ struct GraEngine {
   uint32_t max_upd;          /* max updates per tick */
   uint32_t task_cap;
   uint32_t group_cap;        /* max contiguous shard-groups per tick */
-  /* decode scratch is PARITY-DOUBLED: tick N+1's k_decode runs on the
-   * prep stream under tick N's k_copy (decode is a sparse latency-bound
-   * walk, copy is HBM-bound — they compose), so consecutive ticks must
-   * not share totals/scans/reccache. scratch_used_ev[p] (recorded after
-   * a tick's last scratch reader, k_rundesc) gates reuse. */
-  wb::WalkTotals *d_totals_b[2] = {nullptr, nullptr};
-  uint2 *d_partial_b[2] = {nullptr, nullptr};
-  uint2 *d_bsums_b[2] = {nullptr, nullptr};
-  wb::Rec *d_reccache_b[2] = {nullptr, nullptr};
-  hipEvent_t scratch_used_ev[2] = {nullptr, nullptr};
+  /* decode scratch is shared by consecutive ticks: every kernel touching
+   * it (k_decode .. k_rundesc) runs on `stream`, so the stream orders a
+   * tick's last reader before the next tick's k_decode. Running decode on
+   * the prep stream under the previous tick's copy was measured and
+   * removed. */
+  wb::WalkTotals *d_totals = nullptr;
+  uint2 *d_partial = nullptr;
+  uint2 *d_bsums = nullptr;
+  wb::Rec *d_reccache = nullptr;
   CopyTask *d_tasks = nullptr;
   TickPlace *d_place = nullptr; /* kSlots entries: per-tick placement slot
                                    (the drain D2H snapshot on copyout must
@@ -954,8 +1002,7 @@ struct GraEngine {
    * H2D into buffer B (h2d stream) overlaps the kernels still reading
    * buffer A (main stream). stage_used_ev[b] is recorded on the main
    * stream after the last kernel reading buffer b; the next H2D into b
-   * waits on it. d_stage_blobs/d_stage_descs alias buffer 0 (capacity
-   * checks + call-site compatibility). */
+   * waits on it. */
   uint8_t *d_stage_blobs_bufs[2] = {nullptr, nullptr};
   UpdDesc *d_stage_descs_bufs[2] = {nullptr, nullptr};
   hipEvent_t stage_used_ev[2] = {nullptr, nullptr};
@@ -965,8 +1012,6 @@ struct GraEngine {
    * in-flight SDMA transfers degrade 56 -> 37 GB/s; blocking the host in
    * hipEventSynchronize instead keeps them at full rate. */
   hipEvent_t h2d_gate_ev[2] = {nullptr, nullptr};
-  uint8_t *d_stage_blobs = nullptr;
-  UpdDesc *d_stage_descs = nullptr;
   /* slots + pending ticks */
   Slot slots[kSlots];
   std::deque<TickRec> pending;
@@ -1002,16 +1047,7 @@ struct GraEngine {
 
   int init(const GraEngineOpts &o);
   ~GraEngine();
-  int enqueue_tick(const uint8_t *d_blobs, const UpdDesc *d_descw, uint32_t n,
-                   const std::vector<GroupDesc> &groups, uint64_t blob_bytes,
-                   bool time_h2d, const void *h2d_src = nullptr,
-                   size_t h2d_bytes = 0, uint8_t *d_h2d_dst = nullptr,
-                   const UpdDesc *h_descs_src = nullptr,
-                   const GroupDesc *d_groups_dev = nullptr,
-                   const uint8_t *d_comp = nullptr,
-                   const SnapTask *d_snaptasks = nullptr,
-                   std::vector<uint32_t> &&counts = {},
-                   hipEvent_t window_ev = nullptr);
+  int enqueue_tick(TickInput &in);
   int ingest(bool wait_all);
   int ingest_one(TickRec &t, bool wait);
   int flush_locked();
@@ -1035,7 +1071,7 @@ struct TickPlan {
                                     per-step 20 MB desc rebase + H2D that
                                     throttled the staged leg to ~39 GB/s
                                     happens once per window instead */
-  hipEvent_t consumed_ev = nullptr; /* snappy overlap: recorded after each
+  hipEvent_t consumed_ev = nullptr; /* snappy pre-stage: recorded after each
                                        tick of this window finishes reading
                                        its scratch slots (k_copy); the next
                                        k_snappy of the SAME window waits on
@@ -1139,14 +1175,10 @@ int GraEngine::init(const GraEngineOpts &o) {
   HIP_TRY(hipMalloc(&d_store, opts.store_bytes + 16));
   HIP_TRY(hipMalloc(&d_cursor, 8));
   HIP_TRY(hipMemset(d_cursor, 0, 8));
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(hipMalloc(&d_totals_b[i], (size_t)max_upd * sizeof(wb::WalkTotals)));
-    HIP_TRY(hipMalloc(&d_partial_b[i], (size_t)max_upd * sizeof(uint2)));
-    HIP_TRY(hipMalloc(&d_bsums_b[i], ((size_t)max_upd / 256 + 2) * sizeof(uint2)));
-    HIP_TRY(hipMalloc(&d_reccache_b[i], (size_t)max_upd * 2 * sizeof(wb::Rec)));
-    HIP_TRY(hipEventCreateWithFlags(&scratch_used_ev[i], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(scratch_used_ev[i], stream));
-  }
+  HIP_TRY(hipMalloc(&d_totals, (size_t)max_upd * sizeof(wb::WalkTotals)));
+  HIP_TRY(hipMalloc(&d_partial, (size_t)max_upd * sizeof(uint2)));
+  HIP_TRY(hipMalloc(&d_bsums, ((size_t)max_upd / 256 + 2) * sizeof(uint2)));
+  HIP_TRY(hipMalloc(&d_reccache, (size_t)max_upd * 2 * sizeof(wb::Rec)));
   HIP_TRY(hipMalloc(&d_tasks, (size_t)task_cap * sizeof(CopyTask)));
   HIP_TRY(hipMalloc(&d_place, kSlots * sizeof(TickPlace)));
   HIP_TRY(hipMalloc(&d_groups, (size_t)group_cap * sizeof(GroupDesc)));
@@ -1160,8 +1192,6 @@ int GraEngine::init(const GraEngineOpts &o) {
     HIP_TRY(hipEventCreateWithFlags(&h2d_gate_ev[i], hipEventDisableTiming));
     HIP_TRY(hipEventRecord(h2d_gate_ev[i], h2d));
   }
-  d_stage_blobs = d_stage_blobs_bufs[0];
-  d_stage_descs = d_stage_descs_bufs[0];
   /* epochs must be unique ACROSS engine instances: a thread-local staging
    * chunk could otherwise match a freshly created engine reusing the same
    * heap address (ABA) */
@@ -1169,16 +1199,10 @@ int GraEngine::init(const GraEngineOpts &o) {
   /* staging pinned memory is written by MANY host threads and only read
    * by SDMA H2D: allocate it NON-COHERENT (cacheable on the CPU side) —
    * the default fine-grained pinned memory takes uncached CPU writes on
-   * these hosts and capped the streaming fill around 20 GB/s.
-   * GRA_STAGE_COHERENT=1 restores the default for A/B. */
-  static const unsigned stage_flags = [] {
-    const char *v = getenv("GRA_STAGE_COHERENT");
-    return (v && v[0] == '1') ? hipHostMallocDefault
-                              : hipHostMallocNonCoherent;
-  }();
+   * these hosts and capped the streaming fill around 20 GB/s. */
   for (int i = 0; i < 2; i++) {
     HIP_TRY(hipHostMalloc(&stage[i].pin, opts.staging_bytes + 16,
-                          stage_flags));
+                          hipHostMallocNonCoherent));
     stage[i].descs = (GraUpdateDesc *)malloc((size_t)max_upd * sizeof(GraUpdateDesc));
     stage[i].epoch = g_epoch.fetch_add(1u << 20);
     HIP_TRY(hipEventCreate(&stage[i].free_ev));
@@ -1260,13 +1284,9 @@ GraEngine::~GraEngine() {
     if (stage_used_ev[i]) (void)hipEventDestroy(stage_used_ev[i]);
     if (h2d_gate_ev[i]) (void)hipEventDestroy(h2d_gate_ev[i]);
   }
-  for (int i = 0; i < 2; i++) {
-    for (void *p : {(void *)d_totals_b[i], (void *)d_partial_b[i],
-                    (void *)d_bsums_b[i], (void *)d_reccache_b[i]})
-      if (p) (void)hipFree(p);
-    if (scratch_used_ev[i]) (void)hipEventDestroy(scratch_used_ev[i]);
-  }
-  for (void *p : {(void *)d_store, (void *)d_cursor, (void *)d_tasks,
+  for (void *p : {(void *)d_totals, (void *)d_partial, (void *)d_bsums,
+                  (void *)d_reccache, (void *)d_store, (void *)d_cursor,
+                  (void *)d_tasks,
                   (void *)d_place, (void *)d_groups, (void *)d_err_ring})
     if (p) (void)hipFree(p);
   shards.clear(); /* release run arenas before draining the pool */
@@ -1296,16 +1316,10 @@ int GraEngine::free_slot() {
   }
 }
 
-int GraEngine::enqueue_tick(const uint8_t *d_blobs, const UpdDesc *d_descw,
-                            uint32_t n, const std::vector<GroupDesc> &groups,
-                            uint64_t blob_bytes, bool time_h2d,
-                            const void *h2d_src, size_t h2d_bytes,
-                            uint8_t *d_h2d_dst, const UpdDesc *h_descs_src,
-                            const GroupDesc *d_groups_dev,
-                            const uint8_t *d_comp,
-                            const SnapTask *d_snaptasks,
-                            std::vector<uint32_t> &&counts,
-                            hipEvent_t window_ev) {
+int GraEngine::enqueue_tick(TickInput &in) {
+  const uint32_t n = in.n;
+  const uint64_t blob_bytes = in.blob_bytes;
+  const std::vector<GroupDesc> &groups = *in.groups;
   if (n == 0) return GRA_OK;
   if (n > max_upd) {
     g_err = "tick exceeds max updates per tick";
@@ -1332,8 +1346,7 @@ int GraEngine::enqueue_tick(const uint8_t *d_blobs, const UpdDesc *d_descw,
    * device-cached plan the host copy stayed stale and the error path read
    * garbage groups — replay-tick corruption went undetected) */
   memcpy(sl.h_groups, groups.data(), ngroups * sizeof(GroupDesc));
-  const GroupDesc *groups_for_kernel = d_groups_dev;
-  if (!groups_for_kernel) groups_for_kernel = d_groups;
+  const GroupDesc *groups_for_kernel = in.d_groups ? in.d_groups : d_groups;
   uint32_t tick = tick_id++;
 
   TickRec t;
@@ -1341,162 +1354,109 @@ int GraEngine::enqueue_tick(const uint8_t *d_blobs, const UpdDesc *d_descw,
   t.n = n;
   t.ngroups = ngroups;
   t.blob_bytes = blob_bytes;
-  t.h2d_timed = time_h2d;
-  t.counts = std::move(counts);
+  t.counts = std::move(in.counts);
   for (int i = 0; i < kEventsPerTick; i++) t.ev[i] = get_event();
-  static const bool detailed = [] {
-    const char *v = getenv("GRA_DETAILED_EVENTS");
-    return v && v[0] == '1';
-  }();
-  auto rec = [&](int i) {
-    t.evmask |= 1u << i;
-    return hipEventRecord(t.ev[i], stream);
-  };
+  static const bool detailed = env_flag("GRA_DETAILED_EVENTS");
 
-  if (!d_groups_dev) {
+  if (!in.d_groups) {
     HIP_TRY(hipMemcpyAsync(d_groups, sl.h_groups, ngroups * sizeof(GroupDesc),
                            hipMemcpyHostToDevice, stream));
   }
-  HIP_TRY(rec(0)); /* tick start */
+  HIP_TRY(t.record(kEvTickStart, stream));
+  const uint8_t *d_blobs = in.d_blobs;
+  const UpdDesc *d_descw = in.d_descs;
   int stage_buf = -1;
-  if (h2d_src != nullptr) { /* PCIe-inclusive path: stage blobs (+descs) on
-                             * the dedicated h2d stream, double-buffered —
-                             * this tick's copy overlaps the previous tick's
-                             * kernels (which read the other buffer) */
+  if (in.stage_src != nullptr) { /* PCIe-inclusive path: stage blobs (+descs)
+                                  * on the dedicated h2d stream, double-
+                                  * buffered — this tick's copy overlaps the
+                                  * previous tick's kernels (which read the
+                                  * other buffer) */
     stage_buf = (int)(tick & 1u);
-    if (d_h2d_dst == d_stage_blobs_bufs[0]) { /* engine-managed staging */
-      d_h2d_dst = d_stage_blobs_bufs[stage_buf];
-      d_blobs = d_stage_blobs_bufs[stage_buf];
-      if (h_descs_src) d_descw = d_stage_descs_bufs[stage_buf];
-    }
+    d_blobs = d_stage_blobs_bufs[stage_buf];
+    if (in.h_descs) d_descw = d_stage_descs_bufs[stage_buf];
     /* host gate: the copy that last used this buffer (2 staged ticks ago)
      * must have completed — bounds the SDMA queue to <=2 pending copies
      * (see h2d_gate_ev above for why) */
     HIP_TRY(hipEventSynchronize(h2d_gate_ev[stage_buf]));
     /* previous reader of this buffer must be done before overwrite */
     HIP_TRY(hipStreamWaitEvent(h2d, stage_used_ev[stage_buf], 0));
-    t.evmask |= 1u << 9; /* h2d leg timed on its own stream: ev9 -> ev1 */
-    HIP_TRY(hipEventRecord(t.ev[9], h2d));
-    HIP_TRY(hipMemcpyAsync(d_h2d_dst, h2d_src, h2d_bytes,
-                           hipMemcpyHostToDevice, h2d));
-    if (h_descs_src) {
-      memcpy(sl.h_descs, h_descs_src, (size_t)n * sizeof(UpdDesc));
-      HIP_TRY(hipMemcpyAsync((void *)d_descw, sl.h_descs,
+    HIP_TRY(t.record(kEvH2dStart, h2d)); /* leg timed on its own stream */
+    HIP_TRY(hipMemcpyAsync(d_stage_blobs_bufs[stage_buf], in.stage_src,
+                           in.stage_bytes, hipMemcpyHostToDevice, h2d));
+    if (in.h_descs) {
+      memcpy(sl.h_descs, in.h_descs, (size_t)n * sizeof(UpdDesc));
+      HIP_TRY(hipMemcpyAsync(d_stage_descs_bufs[stage_buf], sl.h_descs,
                              (size_t)n * sizeof(UpdDesc),
                              hipMemcpyHostToDevice, h2d));
     }
-    t.evmask |= 1u << 1;
-    HIP_TRY(hipEventRecord(t.ev[1], h2d));
+    HIP_TRY(t.record(kEvH2dDone, h2d));
     HIP_TRY(hipEventRecord(h2d_gate_ev[stage_buf], h2d));
-    HIP_TRY(hipStreamWaitEvent(stream, t.ev[1], 0)); /* kernels gate on data */
+    /* kernels gate on data */
+    HIP_TRY(hipStreamWaitEvent(stream, t.ev[kEvH2dDone], 0));
   }
   uint32_t nb = (n + 255) / 256;
-  static const bool snappy_overlap = [] { /* A/B escape hatch */
-    const char *v = getenv("GRA_SNAPPY_OVERLAP");
-    return !v || v[0] != '0';
-  }();
-  if (d_snaptasks) { /* config #5 pre-stage: decompress into the blob arena
-                      * on the prep stream, overlapped with the previous
-                      * tick's decode..copy. window_ev (recorded after the
-                      * LAST tick of this same window finished reading the
-                      * scratch) fences window reuse without serializing
-                      * prep behind main. Both kernels are CU-bound, so the
-                      * overlap mostly timeslices — kept because it never
-                      * loses and wins when the main tick has SDMA phases. */
-    hipStream_t ps = snappy_overlap ? prep : stream;
-    if (window_ev && snappy_overlap)
-      HIP_TRY(hipStreamWaitEvent(prep, window_ev, 0));
-    t.evmask |= 1u << 9; /* snappy timed on its own stream: ev9 -> ev8 */
-    HIP_TRY(hipEventRecord(t.ev[9], ps));
-    hipLaunchKernelGGL(k_snappy, dim3(nb), dim3(256), 0, ps, d_comp,
-                       d_snaptasks, n, (uint8_t *)d_blobs, d_err_ring, tick);
+  if (in.d_snaptasks) { /* config #5 pre-stage: decompress into the blob
+                         * arena on the prep stream, overlapped with the
+                         * previous tick's decode..copy. window_ev (recorded
+                         * after the LAST tick of this same window finished
+                         * reading the scratch) fences window reuse without
+                         * serializing prep behind main. Both kernels are
+                         * CU-bound, so the overlap mostly timeslices — kept
+                         * because it never loses and wins when the main
+                         * tick has SDMA phases. */
+    if (in.window_ev) HIP_TRY(hipStreamWaitEvent(prep, in.window_ev, 0));
+    HIP_TRY(t.record(kEvSnappyStart, prep)); /* timed on its own stream */
+    hipLaunchKernelGGL(k_snappy, dim3(nb), dim3(256), 0, prep, in.d_comp,
+                       in.d_snaptasks, n, (uint8_t *)d_blobs, d_err_ring,
+                       tick);
     HIP_TRY(hipGetLastError());
-    t.evmask |= 1u << 8;
-    HIP_TRY(hipEventRecord(t.ev[8], ps));
-    if (snappy_overlap)
-      HIP_TRY(hipStreamWaitEvent(stream, t.ev[8], 0)); /* decode gates on it */
+    HIP_TRY(t.record(kEvSnappyDone, prep));
+    /* decode gates on it */
+    HIP_TRY(hipStreamWaitEvent(stream, t.ev[kEvSnappyDone], 0));
   }
-  /* decode runs on the PREP stream, overlapped with the PREVIOUS tick's
-   * emit/copy on main (decode is a sparse latency-bound walk over record
-   * headers; copy is HBM-bound — they compose). Parity scratch + the
-   * scratch_used gate make consecutive ticks independent; main's scan2
-   * gates on decode-done (ev11). GRA_DECODE_OVERLAP=0 restores the serial
-   * order for A/B. */
-  static const bool decode_overlap = [] {
-    /* default OFF: the A/B measured +1% (noise) on 1 KB records and -9%
-     * on 128 B ones (the cross-stream ev-wait costs more than the
-     * overlap returns; see DESIGN §10.5b zero-sum finding) */
-    const char *v = getenv("GRA_DECODE_OVERLAP");
-    return v && v[0] == '1';
-  }();
-  int par = (int)(tick & 1u);
-  wb::WalkTotals *t_totals = d_totals_b[par];
-  uint2 *t_partial = d_partial_b[par];
-  uint2 *t_bsums = d_bsums_b[par];
-  wb::Rec *t_reccache = d_reccache_b[par];
-  hipStream_t ds = decode_overlap ? prep : stream;
-  if (decode_overlap) {
-    /* previous user of this parity's scratch must have finished reading */
-    HIP_TRY(hipStreamWaitEvent(prep, scratch_used_ev[par], 0));
-    if (stage_buf >= 0) /* staged blobs land via the h2d stream */
-      HIP_TRY(hipStreamWaitEvent(prep, t.ev[1], 0));
-    t.evmask |= 1u << 10;
-    HIP_TRY(hipEventRecord(t.ev[10], prep));
-  }
-  hipLaunchKernelGGL(k_decode, dim3(nb), dim3(256), 0, ds, d_blobs, d_descw,
-                     n, t_totals, opts.max_wb_records, d_err_ring, tick,
-                     t_partial, t_bsums, t_reccache, sl.d_ok);
+  hipLaunchKernelGGL(k_decode, dim3(nb), dim3(256), 0, stream, d_blobs,
+                     d_descw, n, d_totals, opts.max_wb_records, d_err_ring,
+                     tick, d_partial, d_bsums, d_reccache, sl.d_ok);
   HIP_TRY(hipGetLastError());
-  if (decode_overlap) {
-    t.evmask |= 1u << 11;
-    HIP_TRY(hipEventRecord(t.ev[11], prep));
-    HIP_TRY(hipStreamWaitEvent(stream, t.ev[11], 0));
-  } else if (detailed) {
-    HIP_TRY(rec(2)); /* after decode(+scan1) */
-  }
+  if (detailed) HIP_TRY(t.record(kEvAfterDecode, stream)); /* (+scan1) */
   TickPlace *place_slot = d_place + si;
-  hipLaunchKernelGGL(k_scan2, dim3(1), dim3(256), 0, stream, t_bsums, nb,
+  hipLaunchKernelGGL(k_scan2, dim3(1), dim3(256), 0, stream, d_bsums, nb,
                      d_cursor, place_slot, opts.store_bytes, opts.store_ring,
                      task_cap, d_err_ring, tick);
   HIP_TRY(hipGetLastError());
-  if (detailed) HIP_TRY(rec(3)); /* after scan(+reserve) */
+  if (detailed) HIP_TRY(t.record(kEvAfterScan, stream)); /* (+reserve) */
   hipLaunchKernelGGL(k_emit, dim3(nb), dim3(256), 0, stream, d_blobs, d_descw,
-                     n, t_totals, t_partial, t_bsums, place_slot, d_store,
-                     d_tasks, t_reccache);
+                     n, d_totals, d_partial, d_bsums, place_slot, d_store,
+                     d_tasks, d_reccache);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rec(4)); /* after emit (pre-copy) */
+  HIP_TRY(t.record(kEvAfterEmit, stream)); /* pre-copy */
   /* group width by average update size (micro_copy.hip: g32 wins >=512B).
-   * Grid: 2048 blocks = 8/CU = every wave slot — the next tick's decode
-   * can only overlap if the copy leaves wave headroom, hence the
-   * GRA_COPY_GRID knob for the A/B (profiles/r02). */
-  static const uint32_t copy_grid = [] {
-    const char *v = getenv("GRA_COPY_GRID");
-    uint32_t g = v ? (uint32_t)atoi(v) : 2048;
-    return g ? g : 2048;
-  }();
-  if (blob_bytes / (n ? n : 1) >= 512) {
-    hipLaunchKernelGGL((k_copy<32>), dim3(copy_grid), dim3(256), 0, stream,
+   * Grid: 2048 blocks = 8/CU = every wave slot. A sweep of smaller grids
+   * (to leave wave headroom for overlapped work) found none to donate
+   * (profiles/r02). */
+  constexpr uint32_t kCopyGrid = 2048;
+  if (blob_bytes / n >= 512) {
+    hipLaunchKernelGGL((k_copy<32>), dim3(kCopyGrid), dim3(256), 0, stream,
                        d_blobs, d_store, place_slot, d_tasks);
   } else {
-    hipLaunchKernelGGL((k_copy<16>), dim3(copy_grid), dim3(256), 0, stream,
+    hipLaunchKernelGGL((k_copy<16>), dim3(kCopyGrid), dim3(256), 0, stream,
                        d_blobs, d_store, place_slot, d_tasks);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rec(5)); /* after copy */
-  if (window_ev) /* this window's scratch fully consumed */
-    HIP_TRY(hipEventRecord(window_ev, stream));
+  HIP_TRY(t.record(kEvAfterCopy, stream));
+  if (in.window_ev) /* this window's scratch fully consumed */
+    HIP_TRY(hipEventRecord(in.window_ev, stream));
   hipLaunchKernelGGL(k_rundesc, dim3((ngroups + 255) / 256), dim3(256), 0,
-                     stream, groups_for_kernel, ngroups, d_descw, t_totals,
-                     t_partial, t_bsums, n, nb, place_slot, sl.d_rundescs);
+                     stream, groups_for_kernel, ngroups, d_descw, d_totals,
+                     d_partial, d_bsums, n, nb, place_slot, sl.d_rundescs);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(rec(6)); /* main-stream tick end */
-  HIP_TRY(hipEventRecord(scratch_used_ev[par], stream)); /* scratch free */
+  HIP_TRY(t.record(kEvMainEnd, stream));
   if (stage_buf >= 0) /* last reader of this staging buffer has retired */
     HIP_TRY(hipEventRecord(stage_used_ev[stage_buf], stream));
   /* publish run descriptors on the copyout stream, overlapped with the next
    * tick's kernels (per-slot device buffer: no hazard with slot reuse —
-   * ingest waits on ev[7], which gates sl.busy) */
-  HIP_TRY(hipStreamWaitEvent(copyout, t.ev[6], 0));
+   * ingest waits on kEvPublished, which gates sl.busy) */
+  HIP_TRY(hipStreamWaitEvent(copyout, t.ev[kEvMainEnd], 0));
   HIP_TRY(hipMemcpyAsync(sl.h_rundescs, sl.d_rundescs,
                          (size_t)ngroups * sizeof(DevRunDesc),
                          hipMemcpyDeviceToHost, copyout));
@@ -1521,18 +1481,56 @@ int GraEngine::enqueue_tick(const uint8_t *d_blobs, const UpdDesc *d_descw,
       HIP_TRY(hipGetLastError());
     }
   }
-  HIP_TRY(hipEventRecord(t.ev[7], copyout)); /* publication done */
+  HIP_TRY(t.record(kEvPublished, copyout));
   pending.push_back(std::move(t));
   return GRA_OK;
 }
 
 static int fetch_run_impl(GraEngine *e, Run &r);
 
+/* A device run as k_rundesc described it. on_device = false leaves
+ * hdr_cur/payload_cur at their host-only default (ring + drain: the device
+ * bytes recycle, so reads must route through the host arena). */
+static std::shared_ptr<Run> run_from(const DevRunDesc &rd, bool on_device) {
+  auto run = std::make_shared<Run>();
+  run->base_seq = rd.base_seq;
+  run->last_seq = rd.last_seq;
+  run->n_entries = rd.n_entries;
+  run->payload_bytes = rd.payload_bytes;
+  run->pay_rel_base = rd.pay_rel_base;
+  if (on_device) {
+    run->hdr_cur = rd.hdr_off; /* absolute offsets into d_store */
+    run->payload_cur = rd.payload_off;
+  }
+  return run;
+}
+
+/* Roll the shard's submission seq back to the durable boundary and drop
+ * retained-log entries past it: a batch that failed validation (or was
+ * staged on top of one that did) must never be re-served downstream — the
+ * reference's WAL only ever contains accepted batches. Caller holds ss.mu.
+ *
+ * Also the whole handling of a STALE group, on the error path and the
+ * err==0 paths alike: a tick staged BEFORE a corrupt batch's failure was
+ * detected carries base_seqs that assumed the corrupt batch applied. Such
+ * ticks always ingest while the shard is still poisoned
+ * (gra_handle_replicate_response's failure report drains pending ticks
+ * before clearing the flag), so the group is dropped with durable_seq left
+ * alone. Without this, durable_seq re-advances past the rolled-back boundary
+ * and the failed batch is silently skipped on re-pull (follower divergence). */
+static void roll_back_locked(ShardState &ss) {
+  ss.next_seq = ss.durable_seq + 1;
+  while (!ss.log.empty() && ss.log.back().base_seq > ss.durable_seq) {
+    ss.log_used -= ss.log.back().rep.size();
+    ss.log.pop_back();
+  }
+}
+
 int GraEngine::ingest_one(TickRec &t, bool wait) {
   if (wait) {
-    HIP_TRY(hipEventSynchronize(t.ev[7]));
+    HIP_TRY(hipEventSynchronize(t.ev[kEvPublished]));
   } else {
-    hipError_t q = hipEventQuery(t.ev[7]);
+    hipError_t q = hipEventQuery(t.ev[kEvPublished]);
     if (q == hipErrorNotReady) return GRA_NOT_FOUND; /* not done yet */
     if (q != hipSuccess) {
       g_err = std::string("tick event: ") + hipGetErrorString(q);
@@ -1544,40 +1542,29 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
    * stage events are opt-in via GRA_DETAILED_EVENTS; coarse mode lumps
    * decode+scan+emit into emit_ms) */
   float ms;
-  auto has = [&](int i) { return (t.evmask >> i) & 1u; };
-  auto dt = [&](int a, int b) {
-    if (!has(a) || !has(b)) return 0.0;
+  auto dt = [&](TickEvent a, TickEvent b) {
+    if (!t.has(a) || !t.has(b)) return 0.0;
     (void)hipEventElapsedTime(&ms, t.ev[a], t.ev[b]);
     return (double)ms;
   };
-  int prev = 0;
-  if (has(1)) {
-    stats.h2d_ms += dt(has(9) ? 9 : 0, 1); /* ev9->ev1 = copy on the h2d
-                                              stream (overlapped path) */
-    prev = 1;
+  /* the h2d copy and snappy run on their own streams, overlapped with the
+   * previous tick's main-stream kernels: each is its own start->done span.
+   * The main chain starts where the staged data landed, if it was staged. */
+  stats.h2d_ms += dt(kEvH2dStart, kEvH2dDone);
+  stats.snappy_ms += dt(kEvSnappyStart, kEvSnappyDone);
+  TickEvent prev = t.has(kEvH2dDone) ? kEvH2dDone : kEvTickStart;
+  if (t.has(kEvAfterDecode)) {
+    stats.decode_ms += dt(prev, kEvAfterDecode);
+    prev = kEvAfterDecode;
   }
-  if (has(8)) {
-    /* snappy runs on the prep stream, overlapped with the previous tick's
-     * main-stream kernels: ev9->ev8 is its own duration; the main chain
-     * (decode..copy) is unaffected by it */
-    stats.snappy_ms += dt(has(9) ? 9 : prev, 8);
+  if (t.has(kEvAfterScan)) {
+    stats.scan_ms += dt(prev, kEvAfterScan);
+    prev = kEvAfterScan;
   }
-  if (has(10) && has(11)) {
-    /* decode overlapped on the prep stream: its own duration, main chain
-     * unaffected */
-    stats.decode_ms += dt(10, 11);
-  } else if (has(2)) {
-    stats.decode_ms += dt(prev, 2);
-    prev = 2;
-  }
-  if (has(3)) {
-    stats.scan_ms += dt(prev, 3);
-    prev = 3;
-  }
-  stats.emit_ms += dt(prev, 4);
-  stats.copy_ms += dt(4, 5);
-  stats.runfix_ms += dt(5, 6);
-  stats.total_ms += dt(0, 6);
+  stats.emit_ms += dt(prev, kEvAfterEmit);
+  stats.copy_ms += dt(kEvAfterEmit, kEvAfterCopy);
+  stats.runfix_ms += dt(kEvAfterCopy, kEvMainEnd);
+  stats.total_ms += dt(kEvTickStart, kEvMainEnd);
   stats.ticks += 1;
   stats.updates += t.n;
   stats.blob_bytes += t.blob_bytes;
@@ -1617,12 +1604,8 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
          * the reference's repeated DB::Write failures on a full disk
          * (base_seq==0 is the discriminator: real seqs start at 1). */
         ss.poisoned = true;
-        ss.next_seq = ss.durable_seq + 1;
         ss.cnt_failures++;
-        while (!ss.log.empty() && ss.log.back().base_seq > ss.durable_seq) {
-          ss.log_used -= ss.log.back().rep.size();
-          ss.log.pop_back();
-        }
+        roll_back_locked(ss);
         continue;
       }
       if (ss.poisoned) {
@@ -1630,11 +1613,7 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
          * everything staged after the failure is stale — drop the group
          * without touching durable_seq (rd.base_seq-1 may sit past a seq
          * hole), keep next_seq at the durable boundary, prune the log */
-        ss.next_seq = ss.durable_seq + 1;
-        while (!ss.log.empty() && ss.log.back().base_seq > ss.durable_seq) {
-          ss.log_used -= ss.log.back().rep.size();
-          ss.log.pop_back();
-        }
+        roll_back_locked(ss);
         continue;
       }
       uint32_t keep_recs = 0;
@@ -1650,14 +1629,7 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
         keep_seq += c;
       }
       if (!bad) { /* whole group clean */
-        auto run = std::make_shared<Run>();
-        run->base_seq = rd.base_seq;
-        run->last_seq = rd.last_seq;
-        run->n_entries = rd.n_entries;
-        run->payload_bytes = rd.payload_bytes;
-        run->hdr_cur = rd.hdr_off;
-        run->payload_cur = rd.payload_off;
-        run->pay_rel_base = rd.pay_rel_base;
+        auto run = run_from(rd, true);
         if (opts.drain_host && !attach_drain(*run, rd))
           (void)fetch_run_impl(this, *run);
         if (rd.n_entries > 0 && !opts.store_ring) ss.runs.push_back(std::move(run));
@@ -1668,14 +1640,10 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
       }
       if (keep_recs > 0 && have_counts && !opts.store_ring) {
         /* truncated run: the leading clean records are contiguous */
-        auto run = std::make_shared<Run>();
-        run->base_seq = rd.base_seq;
+        auto run = run_from(rd, true);
         run->last_seq = keep_seq;
-        run->n_entries = keep_recs;
-        run->payload_bytes = rd.payload_bytes; /* upper bound; fetch uses hdrs */
-        run->hdr_cur = rd.hdr_off;
-        run->payload_cur = rd.payload_off;
-        run->pay_rel_base = rd.pay_rel_base;
+        run->n_entries = keep_recs; /* payload_bytes stays the whole group's:
+                                       an upper bound; fetch uses hdrs */
         if (opts.drain_host && !attach_drain(*run, rd))
           (void)fetch_run_impl(this, *run);
         ss.runs.push_back(std::move(run));
@@ -1683,91 +1651,49 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
       }
       if (keep_seq > ss.durable_seq) ss.durable_seq = keep_seq;
       ss.poisoned = true;
-      ss.next_seq = ss.durable_seq + 1;
       ss.cnt_failures++; /* ≅ kReplicatorHandleResponseFailure */
-      /* drop retained-log entries past the rolled-back boundary: a batch
-       * that failed validation must never be re-served downstream (the
-       * reference's WAL only ever contains accepted batches) */
-      while (!ss.log.empty() && ss.log.back().base_seq > ss.durable_seq) {
-        ss.log_used -= ss.log.back().rep.size();
-        ss.log.pop_back();
-      }
+      roll_back_locked(ss);
     }
-    for (int i = 0; i < kEventsPerTick; i++) put_event(t.ev[i]);
-    sl.busy = false;
-    return GRA_OK;
-  }
-  /* Stale-group guard for the err==0 paths: a tick staged BEFORE a corrupt
-   * batch's failure was detected carries base_seqs that assumed the corrupt
-   * batch applied. Such ticks always ingest while the shard is still
-   * poisoned (gra_handle_replicate_response's failure report drains pending
-   * ticks before clearing the flag), so drop the group, keep next_seq at
-   * the durable boundary and prune retained-log entries past it — the same
-   * handling as the error path's 'already failed earlier' case. Without
-   * this, durable_seq re-advances past the rolled-back boundary and the
-   * failed batch is silently skipped on re-pull (follower divergence). */
-  auto drop_stale_locked = [&](ShardState &ss) {
-    ss.next_seq = ss.durable_seq + 1;
-    while (!ss.log.empty() && ss.log.back().base_seq > ss.durable_seq) {
-      ss.log_used -= ss.log.back().rep.size();
-      ss.log.pop_back();
-    }
-  };
-  if (opts.store_ring) {
+  } else if (opts.store_ring) {
     /* throughput store: runs are recycled by the ring; keep only seq/stats
      * bookkeeping (Get over recycled regions is undefined by contract) */
     for (uint32_t g = 0; g < t.ngroups; g++) {
       DevRunDesc &rd = sl.h_rundescs[g];
       ShardState &ss = shards[rd.shard];
       std::lock_guard<std::mutex> lk(ss.mu);
-      if (ss.poisoned) {
-        drop_stale_locked(ss);
+      if (ss.poisoned) { /* stale group, see roll_back_locked */
+        roll_back_locked(ss);
         continue;
       }
       if (opts.drain_host && rd.n_entries > 0) {
         /* ring + drain = the production drain shape: the device store is a
-         * staging ring, the host arena keeps the durable run (host-only:
-         * device bytes recycle, so reads route through the host path) */
-        auto run = std::make_shared<Run>();
-        run->base_seq = rd.base_seq;
-        run->last_seq = rd.last_seq;
-        run->n_entries = rd.n_entries;
-        run->payload_bytes = rd.payload_bytes;
-        run->pay_rel_base = rd.pay_rel_base;
+         * staging ring, the host arena keeps the durable run */
+        auto run = run_from(rd, false);
         if (attach_drain(*run, rd)) ss.runs.push_back(std::move(run));
       }
       if (rd.last_seq > ss.durable_seq) ss.durable_seq = rd.last_seq;
       stats.records += rd.n_entries;
       stats.payload_bytes += rd.payload_bytes;
     }
-    for (int i = 0; i < kEventsPerTick; i++) put_event(t.ev[i]);
-    sl.busy = false;
-    return GRA_OK;
-  }
-  for (uint32_t g = 0; g < t.ngroups; g++) {
-    DevRunDesc &rd = sl.h_rundescs[g];
-    ShardState &ss = shards[rd.shard];
-    std::lock_guard<std::mutex> lk(ss.mu);
-    if (ss.poisoned) {
-      drop_stale_locked(ss);
-      continue;
+  } else {
+    for (uint32_t g = 0; g < t.ngroups; g++) {
+      DevRunDesc &rd = sl.h_rundescs[g];
+      ShardState &ss = shards[rd.shard];
+      std::lock_guard<std::mutex> lk(ss.mu);
+      if (ss.poisoned) { /* stale group, see roll_back_locked */
+        roll_back_locked(ss);
+        continue;
+      }
+      if (rd.n_entries > 0) {
+        auto run = run_from(rd, true);
+        if (opts.drain_host && !attach_drain(*run, rd))
+          (void)fetch_run_impl(this, *run); /* eager D2H fallback */
+        ss.runs.push_back(std::move(run));
+      }
+      if (rd.last_seq > ss.durable_seq) ss.durable_seq = rd.last_seq;
+      stats.records += rd.n_entries;
+      stats.payload_bytes += rd.payload_bytes;
     }
-    auto run = std::make_shared<Run>();
-    run->base_seq = rd.base_seq;
-    run->last_seq = rd.last_seq;
-    run->n_entries = rd.n_entries;
-    run->payload_bytes = rd.payload_bytes;
-    run->hdr_cur = rd.hdr_off;      /* absolute offsets into d_store */
-    run->payload_cur = rd.payload_off;
-    run->pay_rel_base = rd.pay_rel_base;
-    if (rd.n_entries > 0) {
-      if (opts.drain_host && !attach_drain(*run, rd))
-        (void)fetch_run_impl(this, *run); /* eager D2H fallback */
-      ss.runs.push_back(std::move(run));
-    }
-    ss.durable_seq = rd.last_seq > ss.durable_seq ? rd.last_seq : ss.durable_seq;
-    stats.records += rd.n_entries;
-    stats.payload_bytes += rd.payload_bytes;
   }
   for (int i = 0; i < kEventsPerTick; i++) put_event(t.ev[i]);
   sl.busy = false;
@@ -1852,12 +1778,17 @@ int GraEngine::stream_tick_locked() {
   }
   /* per-update counts from consecutive base seqs are unavailable here;
    * recover them from the staged batch headers (4B read per update) */
-  std::vector<uint32_t> counts(n);
+  TickInput in;
+  in.n = n;
+  in.groups = &groups;
+  in.blob_bytes = blob_bytes;
+  in.counts.resize(n);
   for (uint32_t i = 0; i < n; i++)
-    counts[i] = wb::fixed32_le(old->pin + ud[i].off + 8);
-  int rc = enqueue_tick(d_stage_blobs, d_stage_descs, n, groups, blob_bytes,
-                        true, old->pin, fill, d_stage_blobs, ud.data(), nullptr,
-                        nullptr, nullptr, std::move(counts));
+    in.counts[i] = wb::fixed32_le(old->pin + ud[i].off + 8);
+  in.stage_src = old->pin;
+  in.stage_bytes = fill;
+  in.h_descs = ud.data();
+  int rc = enqueue_tick(in);
   if (rc != GRA_OK) return rc;
   /* mark the old pinned buffer reusable once its H2D completed (the copy
    * runs on the dedicated h2d stream now) */
@@ -2325,11 +2256,7 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
   uint32_t qtab_size = 64;
   while (qtab_size < 2 * nq) qtab_size <<= 1;
   uint32_t cand_cap = 4 * nq + 1024, tomb_cap = 4096;
-  static const bool force_scan = [] { /* debug: bypass the hash join */
-    const char *v = getenv("GRA_MG_FORCE_SCAN");
-    return v && v[0] == '1';
-  }();
-  bool hashjoin = views.size() <= 65535 && !force_scan;
+  bool hashjoin = views.size() <= 65535;
   if ((mixed && !grow(&mg.d_extra, &mg.extra_cap, nq * sizeof(MgExtra))) ||
       (hashjoin &&
        (!grow(&mg.d_qtab, &mg.qtab_cap, qtab_size * 8) ||
@@ -2457,14 +2384,10 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
                            hipMemcpyDeviceToHost, e->stream) != hipSuccess)
           break;
       } else {
-        static const int use_kpref = [] { /* debug: bypass the filter */
-          const char *v = getenv("GRA_MG_NO_KPREF");
-          return (v && v[0] == '1') ? 0 : 1;
-        }();
         hipLaunchKernelGGL(k_multiget, dim3(nq), dim3(256), 0, e->stream,
                            e->d_store, d_runs, (uint32_t)views.size(), d_keys,
                            d_keybuf, nq, d_valbuf, val_stride, d_out,
-                           mixed ? (MgExtra *)mg.d_extra : nullptr, use_kpref);
+                           mixed ? (MgExtra *)mg.d_extra : nullptr);
         if (hipGetLastError() != hipSuccess) break;
       }
       if (hipMemcpyAsync(out, d_out, nq * sizeof(GraGetResult),
@@ -2701,7 +2624,6 @@ int gra_upload_snappy(GraEngine *e, const uint8_t *comp_arena,
   r->e = e;
   r->snappy = true;
   /* scratch layout: per-update slot, 16-B aligned, +8 B chunk-write slack */
-  std::vector<UpdDesc> tmp; /* not used; offsets computed inline */
   std::vector<GraUpdateDesc> udescs(n);
   std::vector<SnapTask> tasks(n);
   uint64_t scratch = 0;
@@ -2789,11 +2711,7 @@ static TickPlan &plan_for(GraReplay *r, uint64_t first, uint64_t n) {
   } else {
     plan.d_groups = nullptr; /* fall back to per-tick upload */
   }
-  static const bool sort_snap = [] { /* A/B escape hatch */
-    const char *v = getenv("GRA_SNAPPY_SORT");
-    return !v || v[0] != '0';
-  }();
-  if (r->snappy && sort_snap && first + n <= r->snap_tasks.size()) {
+  if (r->snappy && first + n <= r->snap_tasks.size()) {
     /* length-sorted launch order for k_snappy (see TickPlan::d_snap) */
     std::vector<SnapTask> sorted(r->snap_tasks.begin() + first,
                                  r->snap_tasks.begin() + first + n);
@@ -2811,6 +2729,19 @@ static TickPlan &plan_for(GraReplay *r, uint64_t first, uint64_t n) {
     }
   }
   return r->plans.emplace(key, std::move(plan)).first->second;
+}
+
+/* The part of a replay tick that is the same whichever way the blobs reach
+ * the device; the caller adds the blob source. */
+static TickInput plan_input(const GraReplay *r, const TickPlan &plan,
+                            uint64_t first, uint64_t n) {
+  TickInput in;
+  in.n = (uint32_t)n;
+  in.groups = &plan.groups;
+  in.d_groups = plan.d_groups;
+  in.blob_bytes = plan.blob_bytes;
+  in.counts.assign(r->counts.begin() + first, r->counts.begin() + first + n);
+  return in;
 }
 
 /* Pre-build (and device-cache) the tick plan for a replay window so the
@@ -2832,19 +2763,19 @@ int gra_replay_tick(GraReplay *r, uint64_t first, uint64_t n) {
     g_err = "replay window out of range";
     return GRA_ERR;
   }
-  TickPlan &plan = plan_for(r, first, n);
-  std::vector<uint32_t> counts(r->counts.begin() + first,
-                               r->counts.begin() + first + n);
   std::lock_guard<std::mutex> lk(e->mu);
-  if (r->snappy && !plan.consumed_ev)
-    (void)hipEventCreateWithFlags(&plan.consumed_ev, hipEventDisableTiming);
-  return e->enqueue_tick(r->d_blobs, r->d_descs + first, (uint32_t)n,
-                         plan.groups, plan.blob_bytes, false, nullptr, 0,
-                         nullptr, nullptr, plan.d_groups, r->d_comp,
-                         !r->snappy ? nullptr
-                         : plan.d_snap ? plan.d_snap
-                                       : r->d_snaptasks + first,
-                         std::move(counts), plan.consumed_ev);
+  TickPlan &plan = plan_for(r, first, n);
+  TickInput in = plan_input(r, plan, first, n);
+  in.d_blobs = r->d_blobs;
+  in.d_descs = r->d_descs + first;
+  if (r->snappy) {
+    if (!plan.consumed_ev)
+      (void)hipEventCreateWithFlags(&plan.consumed_ev, hipEventDisableTiming);
+    in.d_comp = r->d_comp;
+    in.d_snaptasks = plan.d_snap ? plan.d_snap : r->d_snaptasks + first;
+    in.window_ev = plan.consumed_ev;
+  }
+  return e->enqueue_tick(in);
 }
 
 int gra_replay_tick_h2d(GraReplay *r, uint64_t first, uint64_t n) {
@@ -2865,8 +2796,8 @@ int gra_replay_tick_h2d(GraReplay *r, uint64_t first, uint64_t n) {
     g_err = "h2d window exceeds staging";
     return GRA_ERR;
   }
-  TickPlan &plan = plan_for(r, first, n);
   std::lock_guard<std::mutex> lk(e->mu);
+  TickPlan &plan = plan_for(r, first, n);
   if (!plan.d_ud) {
     /* rebased descs (blob offsets relative to the staged window), uploaded
      * once per window and reused every step */
@@ -2884,12 +2815,11 @@ int gra_replay_tick_h2d(GraReplay *r, uint64_t first, uint64_t n) {
       return GRA_ERR;
     }
   }
-  std::vector<uint32_t> counts(r->counts.begin() + first,
-                               r->counts.begin() + first + n);
-  return e->enqueue_tick(e->d_stage_blobs, plan.d_ud, (uint32_t)n,
-                         plan.groups, plan.blob_bytes, true, r->h_arena + lo,
-                         hi - lo, e->d_stage_blobs, nullptr, plan.d_groups,
-                         nullptr, nullptr, std::move(counts));
+  TickInput in = plan_input(r, plan, first, n);
+  in.stage_src = r->h_arena + lo;
+  in.stage_bytes = hi - lo;
+  in.d_descs = plan.d_ud;
+  return e->enqueue_tick(in);
 }
 
 int gra_replay_sync(GraReplay *r) { return gra_flush(r->e); }
