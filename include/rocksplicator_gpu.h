@@ -138,6 +138,51 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
                  const uint8_t *keybuf, size_t keybuf_len, uint8_t *valbuf,
                  uint32_t val_stride, GraGetResult *out);
 
+/* Ordered range scan served FROM THE DEVICE STORE ≅ ApplicationDB::NewIterator
+ * (rocksdb_admin/application_db.h:55, application_db.cpp:78-83) followed by
+ * Seek(lo) and Next() until hi: every stored key k with lo <= k < hi for
+ * which gra_get(k) would return GRA_OK, in ascending bytewise order of the
+ * STORED key ([cf LE4 | key] for cf != 0 — scan a column family with
+ * cf-prefixed bounds; memcmp on the common prefix, then the shorter key
+ * first), together with its value. lo_len == 0 scans from the first key,
+ * hi == NULL has no upper bound, lo >= hi is an empty result and GRA_OK.
+ *
+ * Device path: collect the in-range entries of the shard's runs, bitonic-sort
+ * them by (key, seq desc), resolve each key from its newest entry and the
+ * covering range tombstones, prefix-sum and emit — all on the GPU; only the
+ * emitted bytes cross PCIe. Runs are unsorted by key, so the work per call is
+ * O(entries in the shard) WHATEVER THE RANGE (a sorted-run index is future
+ * work). A key whose newest entry is a live Merge reports GRA_GET_NEEDS_HOST
+ * with the key only; fold it with gra_get (same contract as gra_multiget).
+ * Host path (served_by = GRA_SCAN_HOST; taken when the shard holds host-origin
+ * runs, when more than 4096 range tombstones meet the range, or when device
+ * staging cannot be allocated): same result, merges folded with the engine's
+ * merge operator, so every entry is GRA_GET_FOUND.
+ *
+ * Entries are written while n < max_entries and the cumulative bytes fit in
+ * cap (an entry costs key_len + val_len, key_len alone for NEEDS_HOST). When
+ * the next entry does not fit and n > 0, more = 1 and the call returns
+ * GRA_OK; resume with lo = last key + "\x00". GRA_BUF_TOO_SMALL when the very
+ * first entry does not fit. Call gra_flush first for linearizable results;
+ * scanning recycled ring-store regions is undefined, as for gra_get. */
+enum { GRA_SCAN_DEVICE = 0, GRA_SCAN_HOST = 1 };
+typedef struct {
+  uint32_t key_off, key_len;  /* stored key bytes, in buf */
+  uint32_t val_off, val_len;  /* value bytes, in buf (FOUND only; else 0,0) */
+  uint32_t status;            /* GRA_GET_FOUND | GRA_GET_NEEDS_HOST */
+  uint32_t _pad;
+} GraScanEntry;
+typedef struct {
+  uint32_t n;           /* entries written */
+  uint32_t more;        /* 1: stopped at max_entries or cap before the range ended */
+  uint32_t served_by;   /* GRA_SCAN_* */
+  uint32_t candidates;  /* device path: point entries collected for the sort; host path: 0 */
+  uint64_t buf_used;
+} GraScanInfo;
+int gra_scan(GraDb *db, const void *lo, size_t lo_len, const void *hi,
+             size_t hi_len, uint32_t max_entries, GraScanEntry *out,
+             uint8_t *buf, size_t cap, GraScanInfo *info);
+
 /* Full-store content checksum for any-size parity ("checksum of
  * checksums"): per record FNV-1a over (seq LE8 | type | key_len LE4 |
  * val_len LE4 | key bytes | val bytes), combined per shard by u64

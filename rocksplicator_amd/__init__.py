@@ -18,6 +18,8 @@ from .ffi import (  # noqa: F401
     GRA_OK,
     GRA_NOT_FOUND,
     GRA_NO_GPU,
+    GRA_SCAN_DEVICE,
+    GRA_SCAN_HOST,
     MERGE_CONCAT,
     MERGE_U64ADD,
 )

@@ -787,6 +787,9 @@ __global__ void k_mg_emit(const uint8_t *__restrict__ store,
   }
 }
 
+/* ---------------- device range scan (gra_scan) ---------------- */
+#include "scan_kernels.h"
+
 /* ---- full-store checksum (parity at any size) ----
  * Same record hash as the oracle's orc_shard_checksum: FNV-1a over
  * (seq LE8 | type | key_len LE4 | val_len LE4 | key | val), u64-ADD
@@ -1033,6 +1036,21 @@ struct GraEngine {
            out_cap = 0, extra_cap = 0, qtab_cap = 0, cands_cap = 0,
            tombs_cap = 0, aux_cap = 0;
   } mg;
+  /* range-scan staging cache (grow-only; guarded by mu) */
+  struct ScCache {
+    RunView *d_runs = nullptr;
+    uint8_t *d_bounds = nullptr, *d_out = nullptr;
+    ScCand *d_cands = nullptr;
+    ScTomb *d_tombs = nullptr;
+    ScItem *d_items = nullptr;
+    ScSum *d_bsums = nullptr;
+    GraScanEntry *d_ents = nullptr;
+    ScCtl *d_ctl = nullptr;
+    ScCtl *h_ctl = nullptr; /* pinned mirror */
+    size_t runs_cap = 0, bounds_cap = 0, out_cap = 0, cands_cap = 0,
+           tombs_cap = 0, items_cap = 0, bsums_cap = 0, ents_cap = 0;
+    uint32_t cand_cap = 0; /* candidate records the sort buffers hold */
+  } sc;
   /* drain-host pinned arena pool. DECLARED BEFORE shards: runs hold
    * shared_ptrs whose deleter returns buffers here, so the pool must be
    * destroyed after the shards release them. */
@@ -1278,6 +1296,11 @@ GraEngine::~GraEngine() {
                   (void *)mg.d_counts})
     if (p) (void)hipFree(p);
   if (mg.h_counts) (void)hipHostFree(mg.h_counts);
+  for (void *p : {(void *)sc.d_runs, (void *)sc.d_bounds, (void *)sc.d_out,
+                  (void *)sc.d_cands, (void *)sc.d_tombs, (void *)sc.d_items,
+                  (void *)sc.d_bsums, (void *)sc.d_ents, (void *)sc.d_ctl})
+    if (p) (void)hipFree(p);
+  if (sc.h_ctl) (void)hipHostFree(sc.h_ctl);
   for (int i = 0; i < 2; i++) {
     if (d_stage_blobs_bufs[i]) (void)hipFree(d_stage_blobs_bufs[i]);
     if (d_stage_descs_bufs[i]) (void)hipFree(d_stage_descs_bufs[i]);
@@ -2454,6 +2477,242 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
     }
   }
   return rc;
+}
+
+/* ---- gra_scan: ordered range scan (≅ ApplicationDB::NewIterator) ---- */
+
+enum { kScanTakeHostPath = 100 }; /* scan_device: not servable on device */
+
+/* Device path over a snapshot of device-resident runs. One sync to learn
+ * the page size, then the result copy. Returns GRA_OK / GRA_BUF_TOO_SMALL /
+ * GRA_ERR, or kScanTakeHostPath when the tombstone list overflows or staging
+ * cannot be allocated. */
+static int scan_device(GraEngine *e, const std::vector<RunView> &views,
+                       uint64_t total_payload, const uint8_t *lo, uint32_t lo_len, const uint8_t *hi,
+                       uint32_t hi_len, bool has_hi, uint32_t max_entries,
+                       GraScanEntry *out, uint8_t *buf, size_t cap,
+                       GraScanInfo *info) {
+  std::lock_guard<std::mutex> lk_engine(e->mu);
+  auto &sc = e->sc;
+  auto grow = [](auto **p, size_t *have, size_t need) {
+    if (*have >= need) return true;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(p, need) != hipSuccess) {
+      (void)hipGetLastError(); /* out of memory is handled: host path */
+      return false;
+    }
+    *have = need;
+    return true;
+  };
+  uint64_t total_entries = 0, max_run = 0;
+  for (const auto &v : views) {
+    total_entries += v.n_entries;
+    max_run = v.n_entries > max_run ? v.n_entries : max_run;
+  }
+  /* a page never holds more than the shard does, whatever the caller's
+   * max_entries / cap */
+  uint64_t ent_cap = max_entries < total_entries ? max_entries : total_entries;
+  uint64_t byte_cap = cap < 0xFFFFFFFFull ? cap : 0xFFFFFFFFull;
+  uint64_t out_cap = byte_cap < total_payload ? byte_cap : total_payload;
+  /* bounds staged zero-padded at 16-B aligned offsets (sc_key_cmp_from) */
+  size_t lo16 = ((size_t)lo_len + 15) & ~(size_t)15;
+  size_t hi16 = ((size_t)hi_len + 15) & ~(size_t)15;
+  std::vector<uint8_t> hb(lo16 + hi16 + 32, 0);
+  if (lo_len) memcpy(hb.data(), lo, lo_len);
+  if (hi_len) memcpy(hb.data() + lo16 + 16, hi, hi_len);
+  auto pref8 = [](const uint8_t *p, uint32_t n) {
+    uint64_t v = 0;
+    for (uint32_t i = 0; i < 8; i++) v = (v << 8) | (i < n ? p[i] : 0);
+    return v;
+  };
+  if (!sc.d_ctl) {
+    if (hipMalloc(&sc.d_ctl, sizeof(ScCtl)) != hipSuccess) {
+      (void)hipGetLastError();
+      sc.d_ctl = nullptr;
+      return kScanTakeHostPath;
+    }
+    if (hipHostMalloc(&sc.h_ctl, sizeof(ScCtl)) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(sc.d_ctl);
+      sc.d_ctl = nullptr;
+      sc.h_ctl = nullptr;
+      return kScanTakeHostPath;
+    }
+  }
+  if (!grow(&sc.d_runs, &sc.runs_cap, views.size() * sizeof(RunView)) ||
+      !grow(&sc.d_bounds, &sc.bounds_cap, hb.size()) ||
+      !grow(&sc.d_tombs, &sc.tombs_cap, (size_t)kScTombCap * sizeof(ScTomb)) ||
+      !grow(&sc.d_ents, &sc.ents_cap,
+            (size_t)ent_cap * sizeof(GraScanEntry) + 16) ||
+      !grow(&sc.d_out, &sc.out_cap, (size_t)out_cap + 16))
+    return kScanTakeHostPath;
+  ScBounds bd = {};
+  bd.lo = sc.d_bounds;
+  bd.hi = sc.d_bounds + lo16 + 16;
+  bd.lo_pref = pref8(lo, lo_len);
+  bd.hi_pref = pref8(hi, hi_len);
+  bd.lo_len = lo_len;
+  bd.hi_len = hi_len;
+  bd.has_hi = has_hi ? 1 : 0;
+  uint32_t cand_cap = sc.cand_cap ? sc.cand_cap : kScFirstCap;
+  uint32_t bx = (uint32_t)((max_run + 255) / 256);
+  if (bx > 1024) bx = 1024;
+  if (bx == 0) bx = 1;
+  const uint8_t *store = e->d_store;
+  hipStream_t st = e->stream;
+  for (int attempt = 0;; attempt++) {
+    uint32_t nblocks = cand_cap / 256;
+    if (!grow(&sc.d_cands, &sc.cands_cap, (size_t)cand_cap * sizeof(ScCand)) ||
+        !grow(&sc.d_items, &sc.items_cap, (size_t)cand_cap * sizeof(ScItem)) ||
+        !grow(&sc.d_bsums, &sc.bsums_cap,
+              ((size_t)nblocks + 1) * sizeof(ScSum)))
+      return kScanTakeHostPath;
+    sc.cand_cap = cand_cap;
+    bool ok = false;
+    do {
+      if (hipMemsetAsync(sc.d_ctl, 0, sizeof(ScCtl), st) != hipSuccess ||
+          hipMemcpyAsync(sc.d_runs, views.data(),
+                         views.size() * sizeof(RunView),
+                         hipMemcpyHostToDevice, st) != hipSuccess ||
+          hipMemcpyAsync(sc.d_bounds, hb.data(), hb.size(),
+                         hipMemcpyHostToDevice, st) != hipSuccess)
+        break;
+      hipLaunchKernelGGL(k_sc_collect, dim3(bx, (uint32_t)views.size()),
+                         dim3(256), 0, st, store, sc.d_runs, bd, sc.d_cands,
+                         cand_cap, sc.d_tombs, kScTombCap, sc.d_ctl);
+      /* bitonic sort, sized for the capacity: stages past the padded
+       * candidate count return at once */
+      hipLaunchKernelGGL(k_sc_sort_tile, dim3(cand_cap / kScTile),
+                         dim3(kScTileThreads), 0, st, store, sc.d_cands,
+                         sc.d_ctl, cand_cap, 2u, kScTile, 1);
+      for (uint32_t k = 2 * kScTile; k != 0 && k <= cand_cap; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= kScTile; j >>= 1)
+          hipLaunchKernelGGL(k_sc_sort_global, dim3(cand_cap / 2 / 256),
+                             dim3(256), 0, st, store, sc.d_cands, sc.d_ctl,
+                             cand_cap, j, k);
+        hipLaunchKernelGGL(k_sc_sort_tile, dim3(cand_cap / kScTile),
+                           dim3(kScTileThreads), 0, st, store, sc.d_cands,
+                           sc.d_ctl, cand_cap, k, k, 0);
+      }
+      hipLaunchKernelGGL(k_sc_resolve, dim3(nblocks), dim3(256), 0, st, store,
+                         sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
+                         kScTombCap, sc.d_items, sc.d_bsums);
+      hipLaunchKernelGGL(k_sc_scan2, dim3(1), dim3(256), 0, st, sc.d_bsums,
+                         nblocks, sc.d_ctl);
+      hipLaunchKernelGGL(k_sc_emit<16>, dim3(cand_cap / 16), dim3(256), 0, st,
+                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.d_ctl,
+                         cand_cap, max_entries, byte_cap, sc.d_out, sc.d_ents);
+      if (hipGetLastError() != hipSuccess) break;
+      if (hipMemcpyAsync(sc.h_ctl, sc.d_ctl, sizeof(ScCtl),
+                         hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        break;
+      ok = true;
+    } while (0);
+    if (!ok) {
+      (void)hipStreamSynchronize(st);
+      g_err = "gra_scan: device op failed";
+      return GRA_ERR;
+    }
+    if (sc.h_ctl->ntomb > kScTombCap) return kScanTakeHostPath;
+    if (sc.h_ctl->ncand <= cand_cap) break;
+    /* the counter kept counting past the cap: grow to it and re-run once
+     * (the snapshot is fixed, so the second count cannot differ) */
+    if (attempt > 0 || sc.h_ctl->ncand > (1u << 30)) return kScanTakeHostPath;
+    while (cand_cap < sc.h_ctl->ncand) cand_cap <<= 1;
+  }
+  const ScCtl &r = *sc.h_ctl;
+  info->candidates = r.ncand;
+  if (r.too_small) return GRA_BUF_TOO_SMALL;
+  /* only the emitted entries and bytes cross PCIe */
+  if ((r.n && hipMemcpyAsync(out, sc.d_ents, (size_t)r.n * sizeof(GraScanEntry),
+                             hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      (r.buf_used && hipMemcpyAsync(buf, sc.d_out, (size_t)r.buf_used,
+                                    hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    g_err = "gra_scan: result copy failed";
+    return GRA_ERR;
+  }
+  info->n = r.n;
+  info->more = r.more;
+  info->buf_used = r.buf_used;
+  return GRA_OK;
+}
+
+int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
+             size_t hi_len, uint32_t max_entries, GraScanEntry *out,
+             uint8_t *buf, size_t cap, GraScanInfo *info) {
+  if (!info || (max_entries && !out) || (cap && !buf) || (lo_len && !lo_)) {
+    g_err = "gra_scan: null argument";
+    return GRA_ERR;
+  }
+  GraEngine *e = db->e;
+  ShardState &ss = e->shards[db->shard];
+  const uint8_t *lo = (const uint8_t *)lo_, *hi = (const uint8_t *)hi_;
+  const bool has_hi = hi != nullptr;
+  if (!has_hi) hi_len = 0;
+  memset(info, 0, sizeof(*info));
+  info->served_by = GRA_SCAN_DEVICE;
+  if (has_hi) { /* lo >= hi: empty range */
+    size_t m = lo_len < hi_len ? lo_len : hi_len;
+    int c = m ? memcmp(lo, hi, m) : 0;
+    if (c > 0 || (c == 0 && lo_len >= hi_len)) return GRA_OK;
+  }
+  /* snapshot the run list, as gra_multiget does */
+  std::vector<RunView> views;
+  std::vector<std::shared_ptr<Run>> runs;
+  bool any_host = false;
+  uint64_t dev_payload = 0;
+  {
+    std::lock_guard<std::mutex> lk(ss.mu);
+    for (const auto &rp : ss.runs) {
+      if (rp->n_entries == 0) continue;
+      runs.push_back(rp);
+      if (rp->hdr_cur == UINT64_MAX)
+        any_host = true;
+      else {
+        views.push_back({rp->hdr_cur, rp->payload_cur, rp->n_entries,
+                         rp->pay_rel_base});
+        dev_payload += rp->payload_bytes;
+      }
+    }
+  }
+  if (runs.empty()) return GRA_OK;
+  if (!any_host && views.size() <= 65535) { /* grid.y = one row per run */
+    /* a stored key is shorter than kScMaxBound, so a longer bound orders
+     * against every key exactly as its first kScMaxBound bytes do */
+    uint32_t l32 = lo_len < kScMaxBound ? (uint32_t)lo_len : kScMaxBound;
+    uint32_t h32 = hi_len < kScMaxBound ? (uint32_t)hi_len : kScMaxBound;
+    int rc = scan_device(e, views, dev_payload, lo, l32, hi, h32, has_hi, max_entries, out,
+                         buf, cap, info);
+    if (rc != kScanTakeHostPath) return rc;
+  }
+  /* host path: host-origin runs in the shard (leader writes, drained
+   * arenas), tombstone-list overflow, or no device staging */
+  info->served_by = GRA_SCAN_HOST;
+  info->candidates = 0;
+  {
+    std::lock_guard<std::mutex> lk(ss.mu);
+    for (auto &r : runs) { /* lazy fetch under the shard lock, as gra_get */
+      int rc = fetch_run_impl(e, *r);
+      if (rc != GRA_OK) return rc;
+    }
+  }
+  ScanResult res;
+  int rc = run_scan(runs, lo, lo_len, has_hi ? hi : nullptr, hi_len,
+                    e->opts.merge_op, max_entries, cap, &res);
+  if (rc == 2) return GRA_BUF_TOO_SMALL;
+  for (size_t i = 0; i < res.items.size(); i++) {
+    const ScanItem &it = res.items[i];
+    out[i] = {it.key_off, it.key_len, it.val_off, it.val_len, GRA_GET_FOUND, 0};
+  }
+  if (!res.buf.empty()) memcpy(buf, res.buf.data(), res.buf.size());
+  info->n = (uint32_t)res.items.size();
+  info->more = res.more ? 1 : 0;
+  info->buf_used = res.buf.size();
+  return GRA_OK;
 }
 
 int gra_shard_checksum(GraDb *db, uint64_t *out) {

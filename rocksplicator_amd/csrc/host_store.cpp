@@ -3,6 +3,9 @@
  * rocksdb_assumption_test.cpp:136-187 (seq accounting). */
 #include "host_store.h"
 
+#include <algorithm>
+#include <queue>
+
 namespace gra {
 
 namespace {
@@ -15,6 +18,52 @@ bool range_covers(const uint8_t *b, size_t bl, const uint8_t *e, size_t el,
   int c2 = memcmp(k, e, kl < el ? kl : el);
   if (c2 > 0 || (c2 == 0 && kl >= el)) return false;
   return true;
+}
+
+/* bytewise key order: memcmp on the common prefix, then shorter first */
+int key_cmp(const uint8_t *a, size_t al, const uint8_t *b, size_t bl) {
+  size_t n = al < bl ? al : bl;
+  int c = n ? memcmp(a, b, n) : 0; /* an empty bound may be a null pointer */
+  if (c != 0) return c;
+  return al < bl ? -1 : (al > bl ? 1 : 0);
+}
+
+using Operand = std::pair<const uint8_t *, uint32_t>;
+
+/* Value of a key from its base Put (if any) and the merge operands above
+ * it, newest..oldest. Caller guarantees have_base || !ops.empty(). */
+void fold_value(bool have_base, const uint8_t *base, uint32_t base_len,
+                const std::vector<Operand> &ops, int merge_op,
+                std::string *out) {
+  if (ops.empty()) {
+    /* no operands above the base: the Put's value verbatim (rocksdb
+     * FullMerge only runs when merge records are newer — mirrored in the
+     * oracle and the device path) */
+    out->assign((const char *)base, base_len);
+    return;
+  }
+  if (merge_op == 1 /* u64add */) {
+    uint64_t acc = 0;
+    if (have_base) memcpy(&acc, base, base_len < 8 ? base_len : 8);
+    for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
+      uint64_t v = 0;
+      memcpy(&v, it->first, it->second < 8 ? it->second : 8);
+      acc += v;
+    }
+    out->assign((const char *)&acc, 8);
+  } else { /* concat with ',' oldest→newest */
+    out->clear();
+    bool first = true;
+    if (have_base) {
+      out->append((const char *)base, base_len);
+      first = false;
+    }
+    for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
+      if (!first) out->push_back(',');
+      first = false;
+      out->append((const char *)it->first, it->second);
+    }
+  }
 }
 
 } /* namespace */
@@ -61,35 +110,7 @@ int run_get(const std::vector<std::shared_ptr<Run>> &runs, const void *key_,
   }
 
   if (!have_base && ops.empty()) return 1;
-  if (ops.empty()) {
-    /* no operands above the base: the Put's value verbatim (rocksdb
-     * FullMerge only runs when merge records are newer — mirrored in the
-     * oracle and the device path) */
-    out->assign((const char *)base, base_len);
-    return 0;
-  }
-  if (merge_op == 1 /* u64add */) {
-    uint64_t acc = 0;
-    if (have_base) memcpy(&acc, base, base_len < 8 ? base_len : 8);
-    for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
-      uint64_t v = 0;
-      memcpy(&v, it->first, it->second < 8 ? it->second : 8);
-      acc += v;
-    }
-    out->assign((const char *)&acc, 8);
-  } else { /* concat with ',' oldest→newest */
-    out->clear();
-    bool first = true;
-    if (have_base) {
-      out->append((const char *)base, base_len);
-      first = false;
-    }
-    for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
-      if (!first) out->push_back(',');
-      first = false;
-      out->append((const char *)it->first, it->second);
-    }
-  }
+  fold_value(have_base, base, base_len, ops, merge_op, out);
   return 0;
 }
 
@@ -123,6 +144,125 @@ void run_probe(const std::vector<std::shared_ptr<Run>> &runs, const void *key_,
       }
     }
   }
+}
+
+int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo_,
+             size_t lo_len, const void *hi_, size_t hi_len, int merge_op,
+             uint32_t max_entries, size_t cap, ScanResult *out) {
+  const uint8_t *lo = (const uint8_t *)lo_, *hi = (const uint8_t *)hi_;
+  out->items.clear();
+  out->buf.clear();
+  out->more = false;
+  if (hi && key_cmp(lo, lo_len, hi, hi_len) >= 0) return 0; /* empty range */
+
+  struct Point {
+    const uint8_t *key, *val;
+    uint64_t seq;
+    uint32_t klen, vlen;
+    uint8_t type;
+  };
+  struct Tomb {
+    const uint8_t *b, *e;
+    uint32_t bl, el;
+    uint64_t seq;
+  };
+  std::vector<Point> pts;
+  std::vector<Tomb> tombs;
+  for (const auto &rp : runs) {
+    const Run &r = *rp;
+    if (r.n_entries == 0) continue;
+    const wb::RecHdr *hdrs = (const wb::RecHdr *)r.hdrs_data();
+    const uint8_t *pay = r.payload_data();
+    for (uint32_t i = 0; i < r.n_entries; i++) {
+      const wb::RecHdr &h = hdrs[i];
+      const uint8_t *k = pay + h.kv_off;
+      if (h.type == wb::kRangeDeletion) {
+        /* keep only tombstones whose [begin, end) meets [lo, hi) */
+        const uint8_t *e = k + h.key_len;
+        if (key_cmp(e, h.val_len, lo, lo_len) <= 0) continue;
+        if (hi && key_cmp(k, h.key_len, hi, hi_len) >= 0) continue;
+        tombs.push_back({k, e, h.key_len, h.val_len, h.seq});
+        continue;
+      }
+      if (key_cmp(k, h.key_len, lo, lo_len) < 0) continue;
+      if (hi && key_cmp(k, h.key_len, hi, hi_len) >= 0) continue;
+      pts.push_back({k, k + h.key_len, h.seq, h.key_len, h.val_len, h.type});
+    }
+  }
+  /* (key asc, seq desc): each key's newest entry leads its group */
+  std::sort(pts.begin(), pts.end(), [](const Point &a, const Point &b) {
+    int c = key_cmp(a.key, a.klen, b.key, b.klen);
+    return c != 0 ? c < 0 : a.seq > b.seq;
+  });
+  /* tombstone sweep: keys ascend, so a tombstone enters once its begin is
+   * reached and is dropped for good once its end is; the heap's top is RD,
+   * the max seq among the tombstones covering the current key */
+  std::sort(tombs.begin(), tombs.end(), [](const Tomb &a, const Tomb &b) {
+    return key_cmp(a.b, a.bl, b.b, b.bl) < 0;
+  });
+  auto by_seq = [](const Tomb *a, const Tomb *b) { return a->seq < b->seq; };
+  std::priority_queue<const Tomb *, std::vector<const Tomb *>,
+                      decltype(by_seq)> open(by_seq);
+  size_t next_tomb = 0;
+
+  std::vector<Operand> ops;
+  std::string val;
+  for (size_t i = 0; i < pts.size();) {
+    const Point &head = pts[i];
+    size_t end = i + 1;
+    while (end < pts.size() &&
+           key_cmp(pts[end].key, pts[end].klen, head.key, head.klen) == 0)
+      end++;
+    while (next_tomb < tombs.size() &&
+           key_cmp(tombs[next_tomb].b, tombs[next_tomb].bl, head.key,
+                   head.klen) <= 0)
+      open.push(&tombs[next_tomb++]);
+    while (!open.empty() &&
+           key_cmp(open.top()->e, open.top()->el, head.key, head.klen) <= 0)
+      open.pop();
+    uint64_t rd = open.empty() ? 0 : open.top()->seq;
+    bool live = (head.type == wb::kValue || head.type == wb::kMerge) &&
+                head.seq > rd;
+    if (live) {
+      if (out->items.size() >= max_entries) {
+        out->more = true;
+        return 0;
+      }
+      /* fold: operands above the newest terminator, all above RD */
+      ops.clear();
+      const uint8_t *base = nullptr;
+      uint32_t base_len = 0;
+      bool have_base = false;
+      for (size_t j = i; j < end && pts[j].seq > rd; j++) {
+        if (pts[j].type == wb::kMerge) {
+          ops.emplace_back(pts[j].val, pts[j].vlen);
+          continue;
+        }
+        if (pts[j].type == wb::kValue) {
+          base = pts[j].val;
+          base_len = pts[j].vlen;
+          have_base = true;
+        }
+        break;
+      }
+      fold_value(have_base, base, base_len, ops, merge_op, &val);
+      if (out->buf.size() + head.klen + val.size() > cap) {
+        if (out->items.empty()) return 2;
+        out->more = true;
+        return 0;
+      }
+      ScanItem it;
+      it.key_off = (uint32_t)out->buf.size();
+      it.key_len = head.klen;
+      out->buf.append((const char *)head.key, head.klen);
+      it.val_off = (uint32_t)out->buf.size();
+      it.val_len = (uint32_t)val.size();
+      out->buf.append(val);
+      out->items.push_back(it);
+    }
+    i = end;
+  }
+  return 0;
 }
 
 bool host_build_run(const uint8_t *rep, size_t len, uint64_t base_seq, Run *out) {

@@ -101,6 +101,27 @@ struct ProbeResult {
 void run_probe(const std::vector<std::shared_ptr<Run>> &runs, const void *key,
                size_t klen, ProbeResult *out);
 
+/* Ordered range scan over a run list (the host side of gra_scan, and the
+ * plain-C++ restatement of the device path): every stored key k with
+ * lo <= k < hi (bytewise; lo_len == 0 = from the first key, hi == nullptr =
+ * unbounded) for which run_get(k) finds a value, ascending, with that value
+ * — merges folded with merge_op. One sort of the in-range point entries by
+ * (key asc, seq desc) plus a sweep over the range tombstones: O(entries log
+ * entries), never one run_get per key. Emission stops at max_entries or when
+ * the next key+value no longer fits in cap bytes (more = true when live keys
+ * remain). Returns 0, or 2 when the very first entry exceeds cap. */
+struct ScanItem {
+  uint32_t key_off, key_len, val_off, val_len; /* into ScanResult::buf */
+};
+struct ScanResult {
+  std::vector<ScanItem> items;
+  std::string buf;
+  bool more = false;
+};
+int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo,
+             size_t lo_len, const void *hi, size_t hi_len, int merge_op,
+             uint32_t max_entries, size_t cap, ScanResult *out);
+
 /* Host apply of one rep blob (leader write path): decodes with wb::walk and
  * builds a Run in the same format the GPU emits. Returns false on corrupt
  * rep. base_seq = first seq to assign. */

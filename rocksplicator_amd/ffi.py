@@ -46,6 +46,35 @@ class GraGetResult(C.Structure):
     _fields_ = [("status", C.c_uint32), ("vlen", C.c_uint32)]
 
 
+GRA_GET_FOUND = 0
+GRA_GET_MISS = 1
+GRA_GET_NEEDS_HOST = 2
+
+GRA_SCAN_DEVICE = 0
+GRA_SCAN_HOST = 1
+
+
+class GraScanEntry(C.Structure):
+    _fields_ = [
+        ("key_off", C.c_uint32),
+        ("key_len", C.c_uint32),
+        ("val_off", C.c_uint32),
+        ("val_len", C.c_uint32),
+        ("status", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
+class GraScanInfo(C.Structure):
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("more", C.c_uint32),
+        ("served_by", C.c_uint32),
+        ("candidates", C.c_uint32),
+        ("buf_used", C.c_uint64),
+    ]
+
+
 class GraDbCounters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "updates_applied", "in_bytes", "apply_failures", "updates_served",
@@ -135,6 +164,9 @@ def load():
     lib.gra_multiget.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(GraKeyRef),
                                  C.c_char_p, C.c_size_t, C.c_char_p,
                                  C.c_uint32, C.POINTER(GraGetResult)]
+    lib.gra_scan.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p,
+                             C.c_size_t, C.c_uint32, C.POINTER(GraScanEntry),
+                             C.c_char_p, C.c_size_t, C.POINTER(GraScanInfo)]
     lib.gra_shard_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.gra_pin_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8))]
     lib.gra_pin_free.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
@@ -402,6 +434,50 @@ class Db:
             else:  # needs host (merge fold / host-origin runs)
                 res.append(self.get(keys[i]))
         return res
+
+    def scan_page(self, lo=b"", hi=None, max_entries=1024, cap=1 << 20):
+        """One page of an ordered range scan over [lo, hi) of the STORED
+        keys (cf keys are [cf LE4 | key]); hi=None is unbounded. Served
+        from the device store when the shard is device-resident; keys whose
+        newest entry is a live Merge are folded here with get(). Returns
+        ([(key, value)], info); info.more says whether the range continues
+        (resume with lo = last key + b"\\x00"). Raises BufferError when the
+        first entry alone exceeds cap."""
+        ents = (GraScanEntry * max(1, max_entries))()
+        buf = C.create_string_buffer(max(1, cap))
+        info = GraScanInfo()
+        rc = self.lib.gra_scan(self.h, lo, len(lo), hi,
+                               0 if hi is None else len(hi), max_entries,
+                               ents, buf, cap, C.byref(info))
+        if rc == GRA_BUF_TOO_SMALL:
+            raise BufferError("gra_scan: first entry exceeds cap")
+        if rc != GRA_OK:
+            raise RuntimeError(f"gra_scan rc={rc}: {last_error(self.lib)}")
+        raw = buf.raw[:info.buf_used]
+        res = []
+        for i in range(info.n):
+            e = ents[i]
+            k = raw[e.key_off:e.key_off + e.key_len]
+            if e.status == GRA_GET_FOUND:
+                res.append((k, raw[e.val_off:e.val_off + e.val_len]))
+            else:  # live merge operands: host fold
+                res.append((k, self.get(k)))
+        return res, info
+
+    def scan(self, lo=b"", hi=None, limit=None, max_entries=1024,
+             cap=1 << 20):
+        """Generator over (key, value) in [lo, hi), ascending; pages with
+        scan_page until the range ends or `limit` entries were yielded."""
+        left = limit
+        while left is None or left > 0:
+            page = max_entries if left is None else min(max_entries, left)
+            ents, info = self.scan_page(lo, hi, page, cap)
+            yield from ents
+            if not info.more or not ents:
+                return
+            if left is not None:
+                left -= len(ents)
+            lo = ents[-1][0] + b"\x00"
 
     def checksum(self):
         """Order-independent full-store content checksum (device-computed;
