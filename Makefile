@@ -12,7 +12,7 @@ all: rocksplicator_amd/libgra.so oracle/libwb_oracle.so
 build:
 	mkdir -p build
 
-build/engine.o: $(CSRC)/engine.hip $(CSRC)/scan_kernels.h $(CSRC)/wb_format.h $(CSRC)/host_store.h $(CSRC)/snappy.h include/rocksplicator_gpu.h | build
+build/engine.o: $(CSRC)/engine.hip $(CSRC)/part_copy.h $(CSRC)/scan_kernels.h $(CSRC)/wb_format.h $(CSRC)/host_store.h $(CSRC)/snappy.h include/rocksplicator_gpu.h | build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 build/host_store.o: $(CSRC)/host_store.cpp $(CSRC)/host_store.h $(CSRC)/wb_format.h | build
@@ -47,7 +47,7 @@ build/test_cpp_chain: scripts/test_cpp_chain.cpp include/rocksplicator_replicato
 build/bench_stream: scripts/bench_stream.cpp include/rocksplicator_gpu.h rocksplicator_amd/libgra.so | build
 	$(HIPCC) $(HIPFLAGS) $< -Lrocksplicator_amd -lgra -Wl,-rpath,'$$ORIGIN/../rocksplicator_amd' -o $@
 
-build/micro_copy: scripts/micro_copy.hip | build
+build/micro_copy: scripts/micro_copy.hip $(CSRC)/part_copy.h | build
 	$(HIPCC) $(HIPFLAGS) -x hip $< -o $@
 
 build/micro_snappy: scripts/micro_snappy.hip | build

@@ -44,6 +44,7 @@
 
 #include "../../include/rocksplicator_gpu.h"
 #include "host_store.h"
+#include "part_copy.h"
 #include "snappy.h"
 #include "wb_format.h"
 
@@ -76,11 +77,6 @@ struct TickPlace {
   uint64_t payload_bytes;
   uint32_t total_rec;
   uint32_t overflow;
-};
-struct CopyTask {
-  uint64_t src_off; /* into blob arena */
-  uint32_t dst_rel; /* into tick payload region */
-  uint32_t nbytes;
 };
 struct SnapTask { /* one compressed Update payload (config #5) */
   uint64_t comp_off;
@@ -152,6 +148,29 @@ constexpr uint32_t kErrRing = 64;
 constexpr uint32_t kRecCache = 2; /* records cached per update by decode so
                                      emit can skip the second blob walk */
 
+/* Exclusive scan of one (records, payload16) pair per thread over a block of
+ * 256: shuffle scan inside each wave, then a 4-entry cross-wave combine.
+ * Every thread of the block must call it, once per kernel. */
+__device__ __forceinline__ uint2 block_scan256(uint2 v, uint2 *total) {
+  __shared__ uint2 wsum[4];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  uint2 inc = v;
+  for (int ofs = 1; ofs < 64; ofs <<= 1) {
+    uint32_t x = __shfl_up(inc.x, ofs, 64), y = __shfl_up(inc.y, ofs, 64);
+    if (lane >= (uint32_t)ofs) inc = add2(inc, make_uint2(x, y));
+  }
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  uint2 before = make_uint2(0, 0), tot = make_uint2(0, 0);
+  for (uint32_t k = 0; k < 4; k++) {
+    uint2 s = wsum[k];
+    if (k < w) before = add2(before, s);
+    tot = add2(tot, s);
+  }
+  *total = tot;
+  return make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
+}
+
 __global__ void k_decode(const uint8_t *__restrict__ blobs,
                          const UpdDesc *__restrict__ descs, uint32_t n,
                          wb::WalkTotals *__restrict__ totals, uint32_t max_rec,
@@ -159,7 +178,6 @@ __global__ void k_decode(const uint8_t *__restrict__ blobs,
                          uint2 *__restrict__ partial, uint2 *__restrict__ bsums,
                          wb::Rec *__restrict__ reccache,
                          uint8_t *__restrict__ ok_out) {
-  __shared__ uint2 sh[256];
   uint32_t i = blockIdx.x * 256 + threadIdx.x;
   uint2 v = make_uint2(0, 0);
   if (i < n) {
@@ -175,20 +193,10 @@ __global__ void k_decode(const uint8_t *__restrict__ blobs,
     if (!t.ok) atomicAdd(&err_ring[tick % kErrRing], 1u);
     if (t.ok) v = make_uint2(t.n_records, t.payload16);
   }
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int ofs = 1; ofs < 256; ofs <<= 1) {
-    uint2 a = sh[threadIdx.x];
-    uint2 b = threadIdx.x >= (uint32_t)ofs ? sh[threadIdx.x - ofs] : make_uint2(0, 0);
-    __syncthreads();
-    sh[threadIdx.x] = add2(a, b);
-    __syncthreads();
-  }
-  if (i < n) {
-    uint2 inc = sh[threadIdx.x];
-    partial[i] = make_uint2(inc.x - v.x, inc.y - v.y); /* exclusive-in-block */
-  }
-  if (threadIdx.x == 255) bsums[blockIdx.x] = sh[255];
+  uint2 tot;
+  uint2 excl = block_scan256(v, &tot);
+  if (i < n) partial[i] = excl; /* exclusive-in-block */
+  if (threadIdx.x == 255) bsums[blockIdx.x] = tot;
 }
 
 __global__ void k_scan2(uint2 *__restrict__ bsums, uint32_t nblocks,
@@ -196,29 +204,21 @@ __global__ void k_scan2(uint2 *__restrict__ bsums, uint32_t nblocks,
                         TickPlace *__restrict__ place, uint64_t cap, int ring,
                         uint32_t task_cap, uint32_t *__restrict__ err_ring,
                         uint32_t tick) {
-  /* single block of 256; sequential chunks with carry; exclusive in place;
+  /* single block of 256, one pass: thread t owns the contiguous block sums
+   * [t*per, t*per + per), the block scans the 256 chunk totals, and each
+   * thread writes its exclusive prefixes back in place;
    * bsums[nblocks] = grand total */
-  __shared__ uint2 sh[256];
-  __shared__ uint2 carry;
-  if (threadIdx.x == 0) carry = make_uint2(0, 0);
-  __syncthreads();
-  for (uint32_t base = 0; base < nblocks; base += 256) {
-    uint32_t i = base + threadIdx.x;
-    uint2 v = i < nblocks ? bsums[i] : make_uint2(0, 0);
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int ofs = 1; ofs < 256; ofs <<= 1) {
-      uint2 a = sh[threadIdx.x];
-      uint2 b = threadIdx.x >= (uint32_t)ofs ? sh[threadIdx.x - ofs] : make_uint2(0, 0);
-      __syncthreads();
-      sh[threadIdx.x] = add2(a, b);
-      __syncthreads();
-    }
-    uint2 inc = add2(sh[threadIdx.x], carry);
-    if (i < nblocks) bsums[i] = make_uint2(inc.x - v.x, inc.y - v.y);
-    __syncthreads();
-    if (threadIdx.x == 255) carry = inc; /* last of chunk = running total */
-    __syncthreads();
+  const uint32_t per = (nblocks + 255) / 256;
+  const uint32_t lo = threadIdx.x * per < nblocks ? threadIdx.x * per : nblocks;
+  const uint32_t hi = lo + per < nblocks ? lo + per : nblocks;
+  uint2 mine = make_uint2(0, 0);
+  for (uint32_t i = lo; i < hi; i++) mine = add2(mine, bsums[i]);
+  uint2 carry;
+  uint2 run = block_scan256(mine, &carry);
+  for (uint32_t i = lo; i < hi; i++) {
+    uint2 v = bsums[i];
+    bsums[i] = run;
+    run = add2(run, v);
   }
   if (threadIdx.x == 0) {
     bsums[nblocks] = carry;
@@ -320,10 +320,9 @@ __global__ void k_emit(const uint8_t *__restrict__ blobs,
   }
 }
 
-/* G-lane-group cooperative copy, dword funnel for misaligned sources (blob
- * arena is over-allocated by 16 B so the +1 word read never faults).
- * Measured on gfx950 (scripts/micro_copy.hip): the dwordx4-store variant
- * below is +52%/+24% over this at 1KB/128B values. */
+/* G-lane-group cooperative byte copy, dword funnel for misaligned sources
+ * (the arenas are over-allocated by 16 B so the +1 word read never faults).
+ * Used by the range-scan emit (scan_kernels.h). */
 template <int G>
 __device__ __forceinline__ void copy_dword(uint8_t *dst, const uint8_t *src,
                                            uint32_t n, uint32_t lane) {
@@ -348,54 +347,19 @@ __device__ __forceinline__ void copy_dword(uint8_t *dst, const uint8_t *src,
   if (lane < tail) dst[done + lane] = src[done + lane];
 }
 
-/* dwordx4 stores + dword-funnel gather; needs 16B-aligned dst (record slots
- * are 16B-aligned; value slices at +klen are aligned for 16B keys). */
-template <int G>
-__device__ __forceinline__ void copy_dwordx4(uint8_t *dst, const uint8_t *src,
-                                             uint32_t n, uint32_t lane) {
-  if (((uintptr_t)dst & 15) != 0) {
-    copy_dword<G>(dst, src, n, lane);
-    return;
-  }
-  uint32_t r = (uint32_t)((uintptr_t)src & 3);
-  const uint32_t *asrc = (const uint32_t *)(src - r);
-  uint4 *d4 = (uint4 *)dst;
-  uint32_t nc = n >> 4;
-  if (r == 0) {
-    for (uint32_t c = lane; c < nc; c += G) {
-      uint32_t w = c * 4;
-      d4[c] = make_uint4(asrc[w], asrc[w + 1], asrc[w + 2], asrc[w + 3]);
-    }
-  } else {
-    uint32_t sh = 8 * r, ish = 32 - sh;
-    for (uint32_t c = lane; c < nc; c += G) {
-      uint32_t w = c * 4;
-      uint32_t a0 = asrc[w], a1 = asrc[w + 1], a2 = asrc[w + 2],
-               a3 = asrc[w + 3], a4 = asrc[w + 4];
-      d4[c] = make_uint4((a0 >> sh) | (a1 << ish), (a1 >> sh) | (a2 << ish),
-                         (a2 >> sh) | (a3 << ish), (a3 >> sh) | (a4 << ish));
-    }
-  }
-  uint32_t done = nc << 4;
-  for (uint32_t b = done + lane; b < n; b += G) dst[b] = src[b];
-}
-
-template <int G>
+/* K4: partition copy (part_copy.h). Tasks come in key/value pairs, two per
+ * record, as k_emit wrote them. G lanes per record, R wave-steps of loads in
+ * flight, UNAL = unaligned dwordx4 loads instead of the alignbyte funnel. */
+template <int G, int R, bool UNAL>
 __global__ void __launch_bounds__(256) k_copy(const uint8_t *__restrict__ blobs,
                                               uint8_t *__restrict__ store,
                                               const TickPlace *__restrict__ place,
                                               const CopyTask *__restrict__ tasks) {
   if (place->overflow) return;
-  uint32_t ntasks = place->total_rec * 2;
-  uint32_t lane = threadIdx.x & (G - 1);
-  uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) / G;
-  uint32_t ngroups = (gridDim.x * blockDim.x) / G;
-  uint8_t *pay_region = store + place->payload_off;
-  for (uint32_t t = g; t < ntasks; t += ngroups) {
-    CopyTask tk = tasks[t];
-    if (tk.nbytes == 0) continue;
-    copy_dwordx4<G>(pay_region + tk.dst_rel, blobs + tk.src_off, tk.nbytes, lane);
-  }
+  uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  pcopy::part_copy<G, R, UNAL>(blobs, store + place->payload_off, tasks,
+                               place->total_rec, wave, nwaves);
 }
 
 /* Drain-host mode (the north star's literal "drain sorted runs back to the
@@ -957,6 +921,7 @@ struct GraEngine {
   /* tick scratch */
   uint32_t max_upd;          /* max updates per tick */
   uint32_t task_cap;
+  uint32_t copy_grid; /* k_copy blocks; GRA_COPY_GRID overrides (tests) */
   uint32_t group_cap;        /* max contiguous shard-groups per tick */
   /* decode scratch is shared by consecutive ticks: every kernel touching
    * it (k_decode .. k_rundesc) runs on `stream`, so the stream orders a
@@ -1167,6 +1132,11 @@ int GraEngine::init(const GraEngineOpts &o) {
   if (opts.max_wb_records == 0) opts.max_wb_records = 1024;
   max_upd = 1u << 20;
   task_cap = 4u << 20;
+  copy_grid = 2048; /* 8 blocks per CU */
+  if (const char *g = getenv("GRA_COPY_GRID")) {
+    long v = atol(g);
+    copy_grid = (uint32_t)(v < 1 ? 1 : v > 2048 ? 2048 : v);
+  }
   group_cap = opts.nshards + 1 > 65536 ? opts.nshards + 1 : 65536;
   (void)hipGetLastError(); /* consume any sticky per-thread error a prior
                               (possibly intentionally failing) call left —
@@ -1453,17 +1423,25 @@ int GraEngine::enqueue_tick(TickInput &in) {
                      d_tasks, d_reccache);
   HIP_TRY(hipGetLastError());
   HIP_TRY(t.record(kEvAfterEmit, stream)); /* pre-copy */
-  /* group width by average update size (micro_copy.hip: g32 wins >=512B).
-   * Grid: 2048 blocks = 8/CU = every wave slot. A sweep of smaller grids
-   * (to leave wave headroom for overlapped work) found none to donate
-   * (profiles/r02). */
-  constexpr uint32_t kCopyGrid = 2048;
-  if (blob_bytes / n >= 512) {
-    hipLaunchKernelGGL((k_copy<32>), dim3(kCopyGrid), dim3(256), 0, stream,
-                       d_blobs, d_store, place_slot, d_tasks);
-  } else {
-    hipLaunchKernelGGL((k_copy<16>), dim3(kCopyGrid), dim3(256), 0, stream,
-                       d_blobs, d_store, place_slot, d_tasks);
+  /* lanes per record by average update size, so a record's 16 B chunks
+   * about fill its lane group; each shape's R and load flavour are the
+   * fastest measured (scripts/micro_copy.hip, profiles/copy64). The grid is
+   * 8 blocks per CU; 4 to 32 per CU measured the same. */
+  {
+    const size_t avg = blob_bytes / n;
+    const dim3 grid(copy_grid), blk(256);
+    if (avg >= 768)
+      hipLaunchKernelGGL((k_copy<64, 4, false>), grid, blk, 0, stream, d_blobs,
+                         d_store, place_slot, d_tasks);
+    else if (avg >= 384)
+      hipLaunchKernelGGL((k_copy<32, 4, true>), grid, blk, 0, stream, d_blobs,
+                         d_store, place_slot, d_tasks);
+    else if (avg >= 192)
+      hipLaunchKernelGGL((k_copy<16, 4, true>), grid, blk, 0, stream, d_blobs,
+                         d_store, place_slot, d_tasks);
+    else
+      hipLaunchKernelGGL((k_copy<8, 4, true>), grid, blk, 0, stream, d_blobs,
+                         d_store, place_slot, d_tasks);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(t.record(kEvAfterCopy, stream));

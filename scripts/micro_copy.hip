@@ -1,7 +1,9 @@
 /* micro_copy.hip — A/B copy-variant microbench for the partition-copy kernel.
  * Tests correctness + bandwidth of byte-granular copies with misaligned
  * sources (the apply path's payload gather): dword funnel vs unaligned
- * vector loads, at several lane-group widths.
+ * vector loads, at several lane-group widths; and the engine's current
+ * kernel (new/...), which includes ../rocksplicator_amd/csrc/part_copy.h.
+ * Args: [records=200000] [value bytes=1024] [key bytes=16].
  * Build: hipcc --offload-arch=gfx950 -O3 scripts/micro_copy.hip -o build/micro_copy
  */
 #include <hip/hip_runtime.h>
@@ -10,6 +12,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+
+#include "../rocksplicator_amd/csrc/part_copy.h"
 
 #define CHECK(x)                                                      \
   do {                                                                \
@@ -144,12 +148,28 @@ __global__ void __launch_bounds__(256) k_bench(const uint8_t *__restrict__ src,
   }
 }
 
+/* new: the engine's partition copy (part_copy.h): batched + prefetched task
+ * fetch, G lanes per record, R wave-steps of loads in flight, unaligned
+ * dwordx4 loads (U=1) or the alignbyte funnel (U=0), nontemporal hints (NT).
+ * Tasks come in key/value pairs, as k_emit writes them. */
+static_assert(sizeof(Task) == sizeof(gra::CopyTask), "task layout");
+template <int G, int R, bool U, int NT>
+__global__ void __launch_bounds__(256) k_new(const uint8_t *__restrict__ src,
+                                             uint8_t *__restrict__ dst,
+                                             const Task *__restrict__ tasks,
+                                             uint32_t ntasks) {
+  uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  gra::pcopy::part_copy<G, R, U, NT>(src, dst, (const gra::CopyTask *)tasks,
+                                     ntasks / 2, wave, nwaves);
+}
+
 int main(int argc, char **argv) {
   /* task mix mirroring config #3: per record a 16B key task (src misaligned)
    * + a 1024B value task; dst 16B-aligned record slots */
   uint32_t nrec = argc > 1 ? atoi(argv[1]) : 200000;
   uint32_t vlen = argc > 2 ? atoi(argv[2]) : 1024;
-  uint32_t klen = 16;
+  uint32_t klen = argc > 3 ? atoi(argv[3]) : 16; /* != 16: misaligned dst */
   uint64_t src_bytes = (uint64_t)nrec * (klen + vlen + 23) + 64;
   uint64_t rec16 = (klen + vlen + 15) & ~15u;
   uint64_t dst_bytes = (uint64_t)nrec * rec16 + 64;
@@ -221,5 +241,20 @@ int main(int argc, char **argv) {
     hipLaunchKernelGGL((k_bench<2, 16, 2, 0>), dim3(2048), blk, 0, 0, d_src,
                        d_dst, d_tasks, nt);
   });
+  /* new kernel: lane mapping (G) x batches of R wave-steps in flight x
+   * load flavour (U) x nontemporal hints (NT: 1 loads, 2 stores) */
+#define RUNN(G, R, U, NT, NB) run("new/g" #G "/r" #R "/u" #U "/nt" #NT "/b" #NB, [&] { \
+    hipLaunchKernelGGL((k_new<G, R, U, NT>), dim3(NB), blk, 0, 0, d_src, d_dst, d_tasks, nt); })
+  RUNN(64, 1, 1, 0, 2048); RUNN(64, 2, 1, 0, 2048); RUNN(64, 4, 1, 0, 2048); RUNN(64, 8, 1, 0, 2048);
+  RUNN(64, 2, 0, 0, 2048); RUNN(64, 4, 0, 0, 2048);
+  RUNN(32, 1, 1, 0, 2048); RUNN(32, 2, 1, 0, 2048); RUNN(32, 4, 1, 0, 2048); RUNN(32, 4, 0, 0, 2048);
+  RUNN(16, 2, 1, 0, 2048); RUNN(16, 4, 1, 0, 2048); RUNN(16, 4, 0, 0, 2048);
+  RUNN(8, 2, 1, 0, 2048); RUNN(8, 4, 1, 0, 2048); RUNN(8, 4, 0, 0, 2048);
+  /* grid: 4 / 16 / 32 blocks per CU */
+  RUNN(64, 4, 1, 0, 1024); RUNN(64, 4, 1, 0, 4096); RUNN(64, 2, 1, 0, 4096); RUNN(64, 2, 1, 0, 8192);
+  RUNN(32, 2, 1, 0, 4096); RUNN(16, 4, 1, 0, 4096); RUNN(8, 4, 1, 0, 4096);
+  /* cache-policy hints */
+  RUNN(64, 4, 1, 1, 2048); RUNN(64, 4, 1, 2, 2048); RUNN(64, 4, 1, 3, 2048);
+  RUNN(8, 4, 1, 3, 2048);
   return 0;
 }
