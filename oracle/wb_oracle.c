@@ -723,12 +723,14 @@ int orc_snappy_decompress(const uint8_t *src, size_t slen, uint8_t *dst,
   while (ip < slen) {
     uint8_t tag = src[ip++];
     if ((tag & 3) == 0) { /* literal */
-      uint32_t len = (tag >> 2) + 1;
+      /* 64-bit: four length bytes of 0xFF mean len 2^32, which a 32-bit
+       * len + 1 wraps to an (accepted) empty literal */
+      uint64_t len = (tag >> 2) + 1;
       if (len > 60) {
-        uint32_t nb = len - 60;
+        uint32_t nb = (uint32_t)len - 60;
         if (ip + nb > slen) return 2;
         len = 0;
-        for (uint32_t b = 0; b < nb; b++) len |= (uint32_t)src[ip + b] << (8 * b);
+        for (uint32_t b = 0; b < nb; b++) len |= (uint64_t)src[ip + b] << (8 * b);
         len += 1;
         ip += nb;
       }
