@@ -65,6 +65,10 @@ typedef struct GraEngineOpts {
                               memtable buffers at flush (the literal
                               "drain to host memtables" mode; default 0 =
                               device-resident store with lazy fetch) */
+  int fold_on_device;      /* 1: gra_multiget and gra_scan fold live merge
+                              operands on the device and report GRA_GET_FOUND
+                              (see both for what still reports NEEDS_HOST);
+                              default 0 = every such key is GRA_GET_NEEDS_HOST */
 } GraEngineOpts;
 
 void gra_engine_opts_init(GraEngineOpts *opts); /* fill defaults */
@@ -122,10 +126,28 @@ int gra_drain_prewarm(GraEngine *e, size_t bytes, uint32_t count);
  * in rocksplicator deployments — ApplicationDB::Get routes to the local db;
  * here the memtable lives in HBM, so the search runs there too: one block
  * per query scanning the shard's runs newest->oldest). Each result value is
- * written at valbuf[q*val_stride] (vlen capped at val_stride). A query
- * whose outcome needs merge-operand folding reports GRA_GET_NEEDS_HOST and
- * is answered by the host path (gra_get) instead. Call gra_flush first for
- * linearizable results. */
+ * written at valbuf[q*val_stride] (the copy is capped at val_stride; vlen is
+ * the true length). Call gra_flush first for linearizable results.
+ *
+ * Merge operands. With T = the key's newest Put/Delete/SingleDelete, RD =
+ * the newest range tombstone covering it and floor = max(T.seq, RD.seq), a
+ * key is "live merge" when it has Merge entries above the floor.
+ *   fold_on_device = 0 (default): every live-merge query reports
+ *     GRA_GET_NEEDS_HOST with vlen 0; answer it with gra_get.
+ *   fold_on_device = 1, GRA_MERGE_U64ADD: the device folds — the base (T's
+ *     value iff T is a Put above RD, else 0) plus every operand above the
+ *     floor, each read as its first min(8, len) bytes little-endian and
+ *     zero-extended, added modulo 2^64. The query reports GRA_GET_FOUND,
+ *     vlen = 8, with the 8 little-endian bytes (min(8, val_stride) copied).
+ *     Chains of any length fold; the result equals gra_get's bit for bit.
+ *   Still GRA_GET_NEEDS_HOST with fold_on_device = 1:
+ *     - GRA_MERGE_CONCAT: the join's candidates are unordered, concat is not
+ *       folded by gra_multiget;
+ *     - any call on a shard that holds host-origin runs (leader writes,
+ *       drained arenas): the device fold is switched off for the whole call,
+ *       because host runs may hold newer entries of a key; live-merge
+ *       queries, including those whose operands straddle device and host
+ *       runs, report NEEDS_HOST as with fold_on_device = 0. */
 enum { GRA_GET_FOUND = 0, GRA_GET_MISS = 1, GRA_GET_NEEDS_HOST = 2 };
 typedef struct {
   uint32_t off, len; /* key slice in keybuf */
@@ -152,15 +174,29 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
  * covering range tombstones, prefix-sum and emit — all on the GPU; only the
  * emitted bytes cross PCIe. Runs are unsorted by key, so the work per call is
  * O(entries in the shard) WHATEVER THE RANGE (a sorted-run index is future
- * work). A key whose newest entry is a live Merge reports GRA_GET_NEEDS_HOST
- * with the key only; fold it with gra_get (same contract as gra_multiget).
+ * work).
+ *
+ * Merge operands on the device path (terms as for gra_multiget):
+ *   fold_on_device = 0 (default): a key whose newest entry is a live Merge
+ *     reports GRA_GET_NEEDS_HOST with the key only; fold it with gra_get.
+ *   fold_on_device = 1: the chain is folded on the device — the operands
+ *     above max(T, RD) that follow the head in the sorted candidates, over
+ *     T's value iff T is a Put above RD — and the entry is GRA_GET_FOUND with
+ *     the folded value: 8 little-endian bytes under GRA_MERGE_U64ADD (any
+ *     chain length); base and operands, oldest to newest, joined by ','
+ *     under GRA_MERGE_CONCAT. Values equal gra_get's bit for bit.
+ *   Still GRA_GET_NEEDS_HOST (key only) with fold_on_device = 1: a
+ *     GRA_MERGE_CONCAT chain of more than 256 operands.
  * Host path (served_by = GRA_SCAN_HOST; taken when the shard holds host-origin
- * runs, when more than 4096 range tombstones meet the range, or when device
- * staging cannot be allocated): same result, merges folded with the engine's
- * merge operator, so every entry is GRA_GET_FOUND.
+ * runs — with or without fold_on_device: nothing is folded on the device
+ * when host runs could hold newer entries of a key —, when more than 4096
+ * range tombstones meet the range, or when device staging cannot be
+ * allocated): same result, merges folded with the engine's merge operator, so
+ * every entry is GRA_GET_FOUND.
  *
  * Entries are written while n < max_entries and the cumulative bytes fit in
- * cap (an entry costs key_len + val_len, key_len alone for NEEDS_HOST). When
+ * cap (an entry costs key_len + val_len, with the FOLDED val_len for a folded
+ * entry, and key_len alone for NEEDS_HOST). When
  * the next entry does not fit and n > 0, more = 1 and the call returns
  * GRA_OK; resume with lo = last key + "\x00". GRA_BUF_TOO_SMALL when the very
  * first entry does not fit. Call gra_flush first for linearizable results;

@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "../../include/rocksplicator_gpu.h"
+#include "fold.h"
 #include "host_store.h"
 #include "part_copy.h"
 #include "snappy.h"
@@ -451,7 +452,7 @@ __global__ void k_multiget(const uint8_t *__restrict__ store,
                            const uint8_t *__restrict__ keybuf, uint32_t nq,
                            uint8_t *__restrict__ valbuf, uint32_t val_stride,
                            GraGetResult *__restrict__ out,
-                           MgExtra *__restrict__ extra) {
+                           MgExtra *__restrict__ extra, int fold_u64) {
   __shared__ uint64_t sh_term_seq[256];
   __shared__ uint64_t sh_term_ref[256]; /* (run<<32)|entry, ~0 = none */
   __shared__ uint64_t sh_merge_seq[256];
@@ -528,6 +529,47 @@ __global__ void k_multiget(const uint8_t *__restrict__ store,
     extra[q].term_type = term_type;
   }
   uint64_t floor_seq = T > RD ? T : RD;
+  if (M > floor_seq && fold_u64) {
+    /* fold_on_device, u64add: a second pass over the runs sums the operands
+     * above the floor (integer adds commute: any order). Long chains land
+     * here — they overflow the hash join's candidate cap. */
+    uint64_t acc = 0;
+    for (uint32_t r = 0; r < nruns; r++) {
+      RunView rv2 = runs[r];
+      const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv2.hdr_off);
+      const uint8_t *pay = store + rv2.payload_off;
+      for (uint32_t i = tid; i < rv2.n_entries; i += blockDim.x) {
+        wb::RecHdr h2 = hdrs[i];
+        if (h2.type != wb::kMerge || h2.seq <= floor_seq ||
+            h2.key_len != klen || h2.kpref != qpref)
+          continue;
+        const uint8_t *k2 = pay + (h2.kv_off - rv2.pay_rel_base);
+        if (dev_memcmp(k2, key, klen) != 0) continue;
+        acc = fold::add_wrap(acc, fold::load_u64le(k2 + klen, h2.val_len));
+      }
+    }
+    __syncthreads(); /* the shared arrays were read above */
+    sh_term_seq[tid] = acc;
+    __syncthreads();
+    for (uint32_t ofs = blockDim.x / 2; ofs > 0; ofs >>= 1) {
+      if (tid < ofs)
+        sh_term_seq[tid] =
+            fold::add_wrap(sh_term_seq[tid], sh_term_seq[tid + ofs]);
+      __syncthreads();
+    }
+    if (tid == 0) {
+      uint64_t v = sh_term_seq[0];
+      if (T > RD && term_type == wb::kValue) /* base: the Put above RD */
+        v = fold::add_wrap(
+            v, fold::load_u64le(store + rv.payload_off +
+                                    (h.kv_off - rv.pay_rel_base) + h.key_len,
+                                h.val_len));
+      fold::store_u64le(valbuf + (size_t)q * val_stride, v, val_stride);
+      out[q].status = GRA_GET_FOUND;
+      out[q].vlen = 8; /* true length (caller sees truncation) */
+    }
+    return;
+  }
   if (M > floor_seq) { /* live merge operands: fold on the host */
     if (tid == 0) {
       out[q].status = GRA_GET_NEEDS_HOST;
@@ -701,6 +743,56 @@ __global__ void k_mg_resolve2(const MgCand *__restrict__ cands,
     winner_ref[c.qidx] = ((unsigned long long)c.run << 32) | c.entry;
 }
 
+/* fold_on_device, u64add: every Merge candidate above its query's floor
+ * max(T, RD) adds its operand into acc[qidx]. Hot counters put most of a
+ * wave on one query, so lanes that share a qidx are summed in the wave
+ * first and their leader issues the one global atomic; a lane alone on its
+ * query adds directly. Integer adds commute: arrival order is immaterial. */
+__global__ void __launch_bounds__(256) k_mg_fold(
+    const uint8_t *__restrict__ store, const RunView *__restrict__ runs,
+    const MgCand *__restrict__ cands, const uint32_t *__restrict__ ncand_p,
+    uint32_t cap, const unsigned long long *__restrict__ term_pack,
+    const unsigned long long *__restrict__ rd_seq,
+    unsigned long long *__restrict__ acc) {
+  uint32_t n = *ncand_p < cap ? *ncand_p : cap;
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t lane = threadIdx.x & 63;
+  bool active = false;
+  uint32_t q = 0;
+  uint64_t v = 0;
+  if (i < n) {
+    MgCand c = cands[i];
+    if (c.type == wb::kMerge) {
+      uint64_t T = term_pack[c.qidx] >> 8, RD = rd_seq[c.qidx];
+      if (c.seq > (T > RD ? T : RD)) {
+        RunView rv = runs[c.run];
+        wb::RecHdr h = ((const wb::RecHdr *)(store + rv.hdr_off))[c.entry];
+        v = fold::load_u64le(store + rv.payload_off +
+                                 (h.kv_off - rv.pay_rel_base) + h.key_len,
+                             h.val_len);
+        q = c.qidx;
+        active = true;
+      }
+    }
+  }
+  /* wave-uniform loop: peel one query per turn */
+  for (unsigned long long m = __ballot(active); m; m = __ballot(active)) {
+    uint32_t leader = (uint32_t)__ffsll((long long)m) - 1;
+    uint32_t lq = __shfl(q, leader, 64);
+    bool mine = active && q == lq;
+    unsigned long long grp = __ballot(mine);
+    uint64_t sum = v;
+    if (grp & (grp - 1)) { /* more than one lane: wave-reduce the group */
+      sum = mine ? v : 0;
+      for (int ofs = 32; ofs > 0; ofs >>= 1)
+        sum = fold::add_wrap(
+            sum, (uint64_t)__shfl_xor((unsigned long long)sum, ofs, 64));
+    }
+    if (lane == leader) atomicAdd(&acc[lq], (unsigned long long)sum);
+    if (mine) active = false;
+  }
+}
+
 __global__ void k_mg_emit(const uint8_t *__restrict__ store,
                           const RunView *__restrict__ runs,
                           const unsigned long long *__restrict__ term_pack,
@@ -709,7 +801,8 @@ __global__ void k_mg_emit(const uint8_t *__restrict__ store,
                           const unsigned long long *__restrict__ winner_ref,
                           uint32_t nq, uint8_t *__restrict__ valbuf,
                           uint32_t val_stride, GraGetResult *__restrict__ out,
-                          MgExtra *__restrict__ extra) {
+                          MgExtra *__restrict__ extra,
+                          const unsigned long long *__restrict__ acc) {
   uint32_t q = blockIdx.x;
   if (q >= nq) return;
   uint64_t tp = term_pack[q];
@@ -722,6 +815,24 @@ __global__ void k_mg_emit(const uint8_t *__restrict__ store,
     extra[q].term_type = ttype;
   }
   uint64_t fl = T > RD ? T : RD;
+  if (M > fl && acc) { /* fold_on_device, u64add: base + k_mg_fold's sum */
+    if (threadIdx.x == 0) {
+      uint64_t v = acc[q];
+      if (T > RD && ttype == wb::kValue) {
+        unsigned long long ref = winner_ref[q];
+        RunView rv = runs[ref >> 32];
+        wb::RecHdr h = ((const wb::RecHdr *)(store + rv.hdr_off))[(uint32_t)ref];
+        v = fold::add_wrap(
+            v, fold::load_u64le(store + rv.payload_off +
+                                    (h.kv_off - rv.pay_rel_base) + h.key_len,
+                                h.val_len));
+      }
+      fold::store_u64le(valbuf + (size_t)q * val_stride, v, val_stride);
+      out[q].status = GRA_GET_FOUND;
+      out[q].vlen = 8; /* true length (caller sees truncation) */
+    }
+    return;
+  }
   if (M > fl) {
     if (threadIdx.x == 0) {
       out[q].status = GRA_GET_NEEDS_HOST;
@@ -994,7 +1105,7 @@ struct GraEngine {
     void *d_qtab = nullptr;  /* hash-join: query fingerprint table (u64) */
     void *d_cands = nullptr; /* MgCand[] matches */
     void *d_tombs = nullptr; /* MgTomb[] range tombstones seen in the scan */
-    void *d_aux = nullptr;   /* 4 x nq u64: term_pack/merge/rd/winner */
+    void *d_aux = nullptr;   /* 5 x nq u64: term_pack/merge/rd/winner/acc */
     uint32_t *d_counts = nullptr; /* {ncand, ntomb} */
     uint32_t *h_counts = nullptr; /* pinned mirror */
     size_t runs_cap = 0, keys_cap = 0, keybuf_cap = 0, valbuf_cap = 0,
@@ -1008,12 +1119,15 @@ struct GraEngine {
     ScCand *d_cands = nullptr;
     ScTomb *d_tombs = nullptr;
     ScItem *d_items = nullptr;
+    ScHead *d_heads = nullptr; /* fold_on_device: live Merge heads */
+    ScFold *d_folds = nullptr; /* fold_on_device: per-candidate fold verdict */
     ScSum *d_bsums = nullptr;
     GraScanEntry *d_ents = nullptr;
     ScCtl *d_ctl = nullptr;
     ScCtl *h_ctl = nullptr; /* pinned mirror */
     size_t runs_cap = 0, bounds_cap = 0, out_cap = 0, cands_cap = 0,
-           tombs_cap = 0, items_cap = 0, bsums_cap = 0, ents_cap = 0;
+           tombs_cap = 0, items_cap = 0, bsums_cap = 0, ents_cap = 0,
+           heads_cap = 0, folds_cap = 0;
     uint32_t cand_cap = 0; /* candidate records the sort buffers hold */
   } sc;
   /* drain-host pinned arena pool. DECLARED BEFORE shards: runs hold
@@ -1268,7 +1382,8 @@ GraEngine::~GraEngine() {
   if (mg.h_counts) (void)hipHostFree(mg.h_counts);
   for (void *p : {(void *)sc.d_runs, (void *)sc.d_bounds, (void *)sc.d_out,
                   (void *)sc.d_cands, (void *)sc.d_tombs, (void *)sc.d_items,
-                  (void *)sc.d_bsums, (void *)sc.d_ents, (void *)sc.d_ctl})
+                  (void *)sc.d_bsums, (void *)sc.d_ents, (void *)sc.d_ctl,
+                  (void *)sc.d_heads, (void *)sc.d_folds})
     if (p) (void)hipFree(p);
   if (sc.h_ctl) (void)hipHostFree(sc.h_ctl);
   for (int i = 0; i < 2; i++) {
@@ -2252,6 +2367,12 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
   uint8_t *d_keybuf = mg.d_keybuf, *d_valbuf = mg.d_valbuf;
   GraGetResult *d_out = mg.d_out;
   const bool mixed = !host_runs.empty();
+  /* The device fold answers FOUND only when it has seen every entry of the
+   * key: a mixed call switches it off, since host runs may hold newer ones
+   * (the seq merge below keeps its cross-half NEEDS_HOST verdict). Concat
+   * needs its operands in order; the candidates are not. */
+  const bool fold_u64 = e->opts.fold_on_device && !mixed &&
+                        e->opts.merge_op == GRA_MERGE_U64ADD;
   std::vector<MgExtra> h_extra;
   /* hash-join path setup: query fingerprint table + candidate buffers */
   uint32_t qtab_size = 64;
@@ -2263,7 +2384,7 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
        (!grow(&mg.d_qtab, &mg.qtab_cap, qtab_size * 8) ||
         !grow(&mg.d_cands, &mg.cands_cap, (size_t)cand_cap * sizeof(MgCand)) ||
         !grow(&mg.d_tombs, &mg.tombs_cap, (size_t)tomb_cap * sizeof(MgTomb)) ||
-        !grow(&mg.d_aux, &mg.aux_cap, (size_t)nq * 8 * 4)))) {
+        !grow(&mg.d_aux, &mg.aux_cap, (size_t)nq * 8 * 5)))) {
     g_err = "gra_multiget: allocation failed";
     return GRA_ERR;
   }
@@ -2346,7 +2467,7 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
         if (hipMemcpyAsync(mg.d_qtab, qtab.data(), qtab_size * 8,
                            hipMemcpyHostToDevice, e->stream) != hipSuccess ||
             hipMemsetAsync(mg.d_counts, 0, 8, e->stream) != hipSuccess ||
-            hipMemsetAsync(mg.d_aux, 0, (size_t)nq * 8 * 4, e->stream) !=
+            hipMemsetAsync(mg.d_aux, 0, (size_t)nq * 8 * 5, e->stream) !=
                 hipSuccess)
           break;
         uint64_t max_entries = 0;
@@ -2364,7 +2485,8 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
         if (hipGetLastError() != hipSuccess) break;
         unsigned long long *aux = (unsigned long long *)mg.d_aux;
         unsigned long long *term_pack = aux, *mergeq = aux + nq,
-                           *rdq = aux + 2 * nq, *winner = aux + 3 * nq;
+                           *rdq = aux + 2 * nq, *winner = aux + 3 * nq,
+                           *accq = aux + 4 * (size_t)nq;
         uint32_t rb = (cand_cap + 255) / 256;
         hipLaunchKernelGGL(k_mg_resolve1, dim3(rb), dim3(256), 0, e->stream,
                            (MgCand *)mg.d_cands, mg.d_counts, cand_cap,
@@ -2376,10 +2498,15 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
         hipLaunchKernelGGL(k_mg_resolve2, dim3(rb), dim3(256), 0, e->stream,
                            (MgCand *)mg.d_cands, mg.d_counts, cand_cap,
                            term_pack, winner);
+        if (fold_u64) /* after resolve1 and tombs: needs T and RD */
+          hipLaunchKernelGGL(k_mg_fold, dim3(rb), dim3(256), 0, e->stream,
+                             e->d_store, d_runs, (MgCand *)mg.d_cands,
+                             mg.d_counts, cand_cap, term_pack, rdq, accq);
         hipLaunchKernelGGL(k_mg_emit, dim3(nq), dim3(64), 0, e->stream,
                            e->d_store, d_runs, term_pack, mergeq, rdq, winner,
                            nq, d_valbuf, val_stride, d_out,
-                           mixed ? (MgExtra *)mg.d_extra : nullptr);
+                           mixed ? (MgExtra *)mg.d_extra : nullptr,
+                           fold_u64 ? accq : (unsigned long long *)nullptr);
         if (hipGetLastError() != hipSuccess) break;
         if (hipMemcpyAsync(mg.h_counts, mg.d_counts, 8,
                            hipMemcpyDeviceToHost, e->stream) != hipSuccess)
@@ -2388,7 +2515,8 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
         hipLaunchKernelGGL(k_multiget, dim3(nq), dim3(256), 0, e->stream,
                            e->d_store, d_runs, (uint32_t)views.size(), d_keys,
                            d_keybuf, nq, d_valbuf, val_stride, d_out,
-                           mixed ? (MgExtra *)mg.d_extra : nullptr);
+                           mixed ? (MgExtra *)mg.d_extra : nullptr,
+                           fold_u64 ? 1 : 0);
         if (hipGetLastError() != hipSuccess) break;
       }
       if (hipMemcpyAsync(out, d_out, nq * sizeof(GraGetResult),
@@ -2472,6 +2600,10 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
                        GraScanInfo *info) {
   std::lock_guard<std::mutex> lk_engine(e->mu);
   auto &sc = e->sc;
+  /* 0 = off (the default chain, kernel for kernel), 1 = concat, 2 = u64add */
+  const int fold = !e->opts.fold_on_device              ? 0
+                   : e->opts.merge_op == GRA_MERGE_U64ADD ? 2
+                                                          : 1;
   auto grow = [](auto **p, size_t *have, size_t need) {
     if (*have >= need) return true;
     if (*p) (void)hipFree(*p);
@@ -2493,7 +2625,10 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
    * max_entries / cap */
   uint64_t ent_cap = max_entries < total_entries ? max_entries : total_entries;
   uint64_t byte_cap = cap < 0xFFFFFFFFull ? cap : 0xFFFFFFFFull;
-  uint64_t out_cap = byte_cap < total_payload ? byte_cap : total_payload;
+  /* a folded value outgrows its records by at most the 8 counter bytes per
+   * key, or one ',' per operand */
+  uint64_t max_out = total_payload + (fold ? 8 * total_entries : 0);
+  uint64_t out_cap = byte_cap < max_out ? byte_cap : max_out;
   /* bounds staged zero-padded at 16-B aligned offsets (sc_key_cmp_from) */
   size_t lo16 = ((size_t)lo_len + 15) & ~(size_t)15;
   size_t hi16 = ((size_t)hi_len + 15) & ~(size_t)15;
@@ -2545,7 +2680,11 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
     if (!grow(&sc.d_cands, &sc.cands_cap, (size_t)cand_cap * sizeof(ScCand)) ||
         !grow(&sc.d_items, &sc.items_cap, (size_t)cand_cap * sizeof(ScItem)) ||
         !grow(&sc.d_bsums, &sc.bsums_cap,
-              ((size_t)nblocks + 1) * sizeof(ScSum)))
+              ((size_t)nblocks + 1) * sizeof(ScSum)) ||
+        (fold &&
+         (!grow(&sc.d_heads, &sc.heads_cap, (size_t)cand_cap * sizeof(ScHead)) ||
+          !grow(&sc.d_folds, &sc.folds_cap,
+                (size_t)cand_cap * sizeof(ScFold)))))
       return kScanTakeHostPath;
     sc.cand_cap = cand_cap;
     bool ok = false;
@@ -2574,14 +2713,46 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
                            dim3(kScTileThreads), 0, st, store, sc.d_cands,
                            sc.d_ctl, cand_cap, k, k, 0);
       }
-      hipLaunchKernelGGL(k_sc_resolve, dim3(nblocks), dim3(256), 0, st, store,
-                         sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
-                         kScTombCap, sc.d_items, sc.d_bsums);
+      if (fold) {
+        /* fold the merge chains first: their sizes feed the prefix sum */
+        hipLaunchKernelGGL(k_sc_heads, dim3(nblocks), dim3(256), 0, st, store,
+                           sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
+                           kScTombCap, sc.d_heads, sc.d_folds);
+        uint32_t fb = cand_cap / 4 < kScFoldWaves ? cand_cap / 4 : kScFoldWaves;
+        if (fold == 2)
+          hipLaunchKernelGGL(k_sc_fold<2>, dim3(fb / 4), dim3(256), 0, st,
+                             store, sc.d_cands, sc.d_heads, sc.d_ctl, cand_cap,
+                             sc.d_folds);
+        else
+          hipLaunchKernelGGL(k_sc_fold<1>, dim3(fb / 4), dim3(256), 0, st,
+                             store, sc.d_cands, sc.d_heads, sc.d_ctl, cand_cap,
+                             sc.d_folds);
+        hipLaunchKernelGGL(k_sc_resolve<true>, dim3(nblocks), dim3(256), 0, st,
+                           store, sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
+                           kScTombCap, sc.d_items, sc.d_bsums, sc.d_folds);
+      } else {
+        hipLaunchKernelGGL(k_sc_resolve<false>, dim3(nblocks), dim3(256), 0, st,
+                           store, sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
+                           kScTombCap, sc.d_items, sc.d_bsums,
+                           (const ScFold *)nullptr);
+      }
       hipLaunchKernelGGL(k_sc_scan2, dim3(1), dim3(256), 0, st, sc.d_bsums,
                          nblocks, sc.d_ctl);
-      hipLaunchKernelGGL(k_sc_emit<16>, dim3(cand_cap / 16), dim3(256), 0, st,
-                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.d_ctl,
-                         cand_cap, max_entries, byte_cap, sc.d_out, sc.d_ents);
+      if (fold == 2)
+        hipLaunchKernelGGL((k_sc_emit<16, 2>), dim3(cand_cap / 16), dim3(256),
+                           0, st, store, sc.d_cands, sc.d_items, sc.d_bsums,
+                           sc.d_ctl, cand_cap, max_entries, byte_cap, sc.d_out,
+                           sc.d_ents, sc.d_folds);
+      else if (fold == 1)
+        hipLaunchKernelGGL((k_sc_emit<16, 1>), dim3(cand_cap / 16), dim3(256),
+                           0, st, store, sc.d_cands, sc.d_items, sc.d_bsums,
+                           sc.d_ctl, cand_cap, max_entries, byte_cap, sc.d_out,
+                           sc.d_ents, sc.d_folds);
+      else
+        hipLaunchKernelGGL((k_sc_emit<16, 0>), dim3(cand_cap / 16), dim3(256),
+                           0, st, store, sc.d_cands, sc.d_items, sc.d_bsums,
+                           sc.d_ctl, cand_cap, max_entries, byte_cap, sc.d_out,
+                           sc.d_ents, (const ScFold *)nullptr);
       if (hipGetLastError() != hipSuccess) break;
       if (hipMemcpyAsync(sc.h_ctl, sc.d_ctl, sizeof(ScCtl),
                          hipMemcpyDeviceToHost, st) != hipSuccess ||

@@ -10,6 +10,9 @@
  *                     tombstones meeting [lo, hi) to a tombstone list
  *   k_sc_sort_tile /  bitonic sort of the candidates by (key asc, seq desc);
  *   k_sc_sort_global  1024-record tiles in LDS, wider strides in global memory
+ *   k_sc_heads /      fold_on_device only: list the live Merge heads with
+ *   k_sc_fold         their RD, then fold each head's operand chain, one
+ *                     wave per head, 64 successors a step
  *   k_sc_resolve      a key's first candidate is its newest entry: it alone
  *                     and the covering tombstones decide the key (fused with
  *                     the in-block half of the prefix sum, like k_decode)
@@ -71,9 +74,29 @@ struct ScItem {
 /* counters + result header, one D2H at the end of the chain */
 struct ScCtl {
   uint32_t ncand, ntomb; /* keep counting past the caps */
-  uint32_t n, more, too_small, _pad;
+  uint32_t n, more, too_small;
+  uint32_t nheads; /* fold_on_device: live Merge heads listed by k_sc_heads */
   uint64_t buf_used;
 };
+
+/* fold_on_device: a live Merge head waiting for its fold, and the verdict.
+ * Both arrays are indexed like the sorted candidates / the head list and
+ * hold at most one record per candidate. */
+struct ScHead {
+  uint64_t rd;  /* max seq of the range tombstones covering the key */
+  uint32_t idx; /* the head's position in the sorted candidates */
+  uint32_t _pad;
+};
+struct ScFold {
+  uint64_t sum;   /* u64add: the folded counter */
+  uint32_t vlen;  /* folded value length */
+  uint32_t flags; /* kScFold* | operand count << 8 */
+};
+constexpr uint32_t kScFoldLive = 1;   /* head.seq > RD */
+constexpr uint32_t kScFoldFolded = 2; /* value computable here: FOUND */
+constexpr uint32_t kScFoldBase = 4;   /* a Put base ends the chain */
+constexpr uint32_t kScFoldWaves = 1024; /* waves the fold kernel is launched
+                                           with; heads are strided over them */
 
 struct ScBounds {
   const uint8_t *lo, *hi; /* device copies, 16-B aligned, zero-padded */
@@ -260,6 +283,171 @@ __global__ void __launch_bounds__(256) k_sc_sort_global(
   }
 }
 
+__device__ inline bool sc_same_key(const uint8_t *store, const ScCand &a,
+                                   const ScCand &b) {
+  return a.pref == b.pref && a.klen == b.klen &&
+         sc_key_cmp_from(store + a.koff, a.klen, store + b.koff, b.klen, 8) ==
+             0;
+}
+
+/* ---- fold_on_device: fold merge chains before the prefix sum ----
+ * Two passes in front of k_sc_resolve, launched only when the engine option
+ * is set, so the default chain is the one above, kernel for kernel.
+ *
+ * k_sc_heads: one thread per sorted candidate. A Merge that leads its key
+ * computes RD = max seq over ALL covering tombstones (an older tombstone
+ * does not kill the head but cuts its chain) and, when live, is appended to
+ * the head list — one atomic per wave, as k_sc_collect does. */
+__global__ void __launch_bounds__(256) k_sc_heads(
+    const uint8_t *__restrict__ store, const ScCand *__restrict__ cands,
+    const ScTomb *__restrict__ tombs, ScCtl *ctl, uint32_t cap,
+    uint32_t tomb_cap, ScHead *__restrict__ heads,
+    ScFold *__restrict__ folds) {
+  uint32_t n = sc_count(ctl, cap);
+  uint32_t ntomb = ctl->ntomb < tomb_cap ? ctl->ntomb : tomb_cap;
+  uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  uint32_t lane = threadIdx.x & 63;
+  bool take = false;
+  uint64_t rd = 0;
+  if (i < n) {
+    ScCand c = cands[i];
+    if (c.type == wb::kMerge &&
+        (i == 0 || !sc_same_key(store, cands[i - 1], c))) {
+      const uint8_t *key = store + c.koff;
+      for (uint32_t t = 0; t < ntomb; t++) {
+        ScTomb tb = tombs[t];
+        if (tb.seq <= rd) continue;
+        const uint8_t *b = store + tb.boff;
+        if (sc_cmp_bytes(b, tb.bl, key, c.klen) <= 0 &&
+            sc_cmp_bytes(key, c.klen, b + tb.bl, tb.el) < 0)
+          rd = tb.seq;
+      }
+      take = c.seq > rd;
+      if (!take) folds[i] = {0, 0, 0}; /* dead: every older entry is too */
+    }
+  }
+  /* every lane of the wave reaches the ballot */
+  unsigned long long m = __ballot(take);
+  if (m) {
+    uint32_t leader = (uint32_t)__ffsll((long long)m) - 1;
+    uint32_t first = 0;
+    if (lane == leader) first = atomicAdd(&ctl->nheads, (uint32_t)__popcll(m));
+    first = __shfl(first, leader, 64);
+    if (take) {
+      uint32_t slot = first + (uint32_t)__popcll(m & ((1ULL << lane) - 1));
+      if (slot < cap) heads[slot] = {rd, i, 0};
+    }
+  }
+}
+
+__device__ inline uint64_t sc_wave_sum(uint64_t v) {
+  for (int ofs = 32; ofs > 0; ofs >>= 1)
+    v += (uint64_t)__shfl_xor((unsigned long long)v, ofs, 64);
+  return v;
+}
+
+/* k_sc_fold: one wave per listed head (heads strided over the launched
+ * waves; the count is read on the device). The head's versions follow it in
+ * (seq desc) order, so the wave takes 64 successors a step, ballots for the
+ * first that is not an operand — another key, a non-Merge, or seq <= RD —
+ * and wave-reduces the operand sum (MODE 2, u64add) or the operand lengths
+ * and count (MODE 1, concat). The entry that ends the chain is the base iff
+ * it is a Put of the same key above RD. A hot counter's chain costs
+ * chain/64 steps of one wave rather than chain steps of one lane; after the
+ * first 64 (most chains end there) a turn takes 4 x 64 successors with their
+ * candidate, key and value loads all in flight before the first ballot, so
+ * the three dependent loads are paid once per 256 operands. */
+struct ScFoldAcc {
+  uint64_t acc; /* u64add: operand sum; concat: value bytes */
+  uint32_t cnt, base;
+  bool over; /* concat: no chain end within kFoldMaxConcatOps */
+};
+
+/* U x 64 successors from pos; true when the chain ended (wave-uniform) */
+template <int MODE, int U>
+__device__ __forceinline__ bool sc_fold_step(
+    const uint8_t *__restrict__ store, const ScCand *__restrict__ cands,
+    uint32_t n, const ScCand &hc, const ScHead &hd, uint32_t pos,
+    uint32_t lane, ScFoldAcc &a) {
+  bool op[U], isbase[U];
+  uint64_t val[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    uint32_t j = pos + u * 64 + lane;
+    op[u] = isbase[u] = false;
+    val[u] = 0;
+    if (j < n) {
+      ScCand c = cands[j];
+      bool mine = c.seq > hd.rd && sc_same_key(store, hc, c);
+      op[u] = mine && c.type == wb::kMerge;
+      isbase[u] = mine && c.type == wb::kValue;
+      if (op[u] || isbase[u]) /* loaded ahead of the ballots */
+        val[u] = MODE == 2
+                     ? fold::load_u64le(store + c.koff + c.klen, c.vlen)
+                     : (uint64_t)c.vlen;
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; u++) {
+    unsigned long long stop = __ballot(!op[u]);
+    uint32_t first = stop ? (uint32_t)__ffsll((long long)stop) - 1 : 64u;
+    if (lane < first) {
+      a.acc = fold::add_wrap(a.acc, val[u]);
+      a.cnt++;
+    } else if (lane == first && isbase[u]) {
+      a.acc = fold::add_wrap(a.acc, val[u]);
+      a.base = 1;
+    }
+    if (stop) return true;
+    if (MODE == 1 &&
+        pos - hd.idx + (u + 1) * 64 > fold::kFoldMaxConcatOps) {
+      a.over = true;
+      return true;
+    }
+  }
+  return false;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_sc_fold(
+    const uint8_t *__restrict__ store, const ScCand *__restrict__ cands,
+    const ScHead *__restrict__ heads, const ScCtl *__restrict__ ctl,
+    uint32_t cap, ScFold *__restrict__ folds) {
+  uint32_t n = sc_count(ctl, cap);
+  uint32_t nheads = ctl->nheads < cap ? ctl->nheads : cap;
+  uint32_t lane = threadIdx.x & 63;
+  uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
+  uint32_t nwaves = gridDim.x * 4;
+  for (uint32_t h = wave; h < nheads; h += nwaves) { /* wave-uniform */
+    ScHead hd = heads[h];
+    ScCand hc = cands[hd.idx];
+    ScFoldAcc a = {0, 0, 0, false};
+    bool done = sc_fold_step<MODE, 1>(store, cands, n, hc, hd, hd.idx, lane, a);
+    for (uint32_t pos = hd.idx + 64; !done; pos += 256)
+      done = sc_fold_step<MODE, 4>(store, cands, n, hc, hd, pos, lane, a);
+    bool over = a.over;
+    uint64_t acc = sc_wave_sum(a.acc);
+    uint32_t nops = (uint32_t)sc_wave_sum(a.cnt);
+    uint32_t has_base = (uint32_t)sc_wave_sum(a.base);
+    if (lane == 0) {
+      ScFold f = {0, 0, kScFoldLive};
+      if (MODE == 2) {
+        f.sum = acc;
+        f.vlen = 8;
+        f.flags |= kScFoldFolded;
+      } else if (!over && nops <= fold::kFoldMaxConcatOps) {
+        /* acc already holds the base's bytes along with the operands' */
+        uint64_t len = fold::concat_len(has_base != 0, 0, acc, nops);
+        if (len + hc.klen < 0xFFFF0000ull) { /* ScItem.cost is 32 bits */
+          f.vlen = (uint32_t)len;
+          f.flags |= kScFoldFolded | (has_base ? kScFoldBase : 0) | (nops << 8);
+        }
+      }
+      folds[hd.idx] = f;
+    }
+  }
+}
+
 /* One thread per sorted candidate. A candidate whose key differs from its
  * predecessor's is the key's newest entry; with RD = max seq of the range
  * tombstones covering the key:
@@ -267,12 +455,15 @@ __global__ void __launch_bounds__(256) k_sc_sort_global(
  *   Merge: seq > RD live (host fold), else dead — every older entry has a
  *   smaller seq and is covered too.
  * seq > RD only asks whether ANY covering tombstone is newer, so tombstones
- * older than the head are skipped without touching their keys. */
+ * older than the head are skipped without touching their keys.
+ * FOLD (fold_on_device): a Merge head takes k_sc_fold's verdict instead —
+ * its folded size feeds the prefix sum, so pagination runs on it. */
+template <bool FOLD>
 __global__ void __launch_bounds__(256) k_sc_resolve(
     const uint8_t *__restrict__ store, const ScCand *__restrict__ cands,
     const ScTomb *__restrict__ tombs, const ScCtl *__restrict__ ctl,
     uint32_t cap, uint32_t tomb_cap, ScItem *__restrict__ items,
-    ScSum *__restrict__ bsums) {
+    ScSum *__restrict__ bsums, const ScFold *__restrict__ folds) {
   __shared__ ScSum sh[256];
   uint32_t n = sc_count(ctl, cap);
   uint32_t ntomb = ctl->ntomb < tomb_cap ? ctl->ntomb : tomb_cap;
@@ -287,7 +478,13 @@ __global__ void __launch_bounds__(256) k_sc_resolve(
              sc_key_cmp_from(store + p.koff, p.klen, store + c.koff, c.klen,
                              8) != 0;
     }
-    if (head && (c.type == wb::kValue || c.type == wb::kMerge)) {
+    if (FOLD && head && c.type == wb::kMerge) {
+      ScFold f = folds[i];
+      if (f.flags & kScFoldLive) {
+        v.cnt = 1;
+        v.bytes = (uint64_t)c.klen + ((f.flags & kScFoldFolded) ? f.vlen : 0u);
+      }
+    } else if (head && (c.type == wb::kValue || c.type == wb::kMerge)) {
       const uint8_t *key = store + c.koff;
       bool live = true;
       for (uint32_t t = 0; t < ntomb && live; t++) {
@@ -363,14 +560,18 @@ __global__ void __launch_bounds__(256) k_sc_scan2(ScSum *__restrict__ bsums,
  * (and value) to out + byte offset and write entry[rank]. Emitted heads form
  * a prefix (rank and bytes are monotone), so exactly one live head — the
  * first that does not fit — sees its predecessor inside the cut and records
- * where the page ended. */
-template <int G>
+ * where the page ended.
+ * FOLD: 0 = off; 1 = concat, 2 = u64add (fold_on_device). A folded Merge
+ * head writes its value here: the 8 counter bytes, or base and operands
+ * oldest to newest joined by ',' — the group walks its (bounded) chain from
+ * the far end, one cooperative copy per entry. */
+template <int G, int FOLD>
 __global__ void __launch_bounds__(256) k_sc_emit(
     const uint8_t *__restrict__ store, const ScCand *__restrict__ cands,
     const ScItem *__restrict__ items, const ScSum *__restrict__ bsums,
     ScCtl *__restrict__ ctl, uint32_t cap, uint32_t max_entries,
     uint64_t byte_cap, uint8_t *__restrict__ out,
-    GraScanEntry *__restrict__ ents) {
+    GraScanEntry *__restrict__ ents, const ScFold *__restrict__ folds) {
   uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) / G;
   uint32_t lane = threadIdx.x & (G - 1);
   if (g >= sc_count(ctl, cap)) return;
@@ -391,14 +592,46 @@ __global__ void __launch_bounds__(256) k_sc_emit(
   ScCand c = cands[g];
   const uint8_t *src = store + c.koff;
   bool found = c.type == wb::kValue;
+  uint32_t vlen = c.vlen;
   copy_dword<G>(out + off, src, c.klen, lane);
   if (found) copy_dword<G>(out + off + c.klen, src + c.klen, c.vlen, lane);
+  if (FOLD && c.type == wb::kMerge) {
+    ScFold f = folds[g];
+    if (f.flags & kScFoldFolded) {
+      found = true;
+      vlen = f.vlen;
+      uint8_t *dst = out + off + c.klen;
+      if (FOLD == 2) {
+        if (lane < 8) dst[lane] = (uint8_t)(f.sum >> (8 * lane));
+      } else {
+        uint32_t nops = f.flags >> 8; /* <= kFoldMaxConcatOps */
+        uint64_t o = 0;
+        bool first = true;
+        if (f.flags & kScFoldBase) {
+          ScCand b = cands[g + nops];
+          copy_dword<G>(dst, store + b.koff + b.klen, b.vlen, lane);
+          o = b.vlen;
+          first = false;
+        }
+        for (uint32_t j = nops; j-- > 0;) { /* oldest operand first */
+          ScCand p = cands[g + j];
+          if (!first) {
+            if (lane == 0) dst[o] = ',';
+            o++;
+          }
+          first = false;
+          copy_dword<G>(dst + o, store + p.koff + p.klen, p.vlen, lane);
+          o += p.vlen;
+        }
+      }
+    }
+  }
   if (lane == 0) {
     GraScanEntry e;
     e.key_off = (uint32_t)off;
     e.key_len = c.klen;
     e.val_off = found ? (uint32_t)off + c.klen : 0u;
-    e.val_len = found ? c.vlen : 0u;
+    e.val_len = found ? vlen : 0u;
     e.status = found ? GRA_GET_FOUND : GRA_GET_NEEDS_HOST;
     e._pad = 0;
     ents[rank] = e;

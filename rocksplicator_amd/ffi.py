@@ -35,6 +35,7 @@ class GraEngineOpts(C.Structure):
         ("retain_log", C.c_int),
         ("log_bytes", C.c_uint64),
         ("drain_host", C.c_int),
+        ("fold_on_device", C.c_int),
     ]
 
 
@@ -293,7 +294,7 @@ class Engine:
 
     def __init__(self, nshards, device=-1, merge_op=0, store_ring=0,
                  store_bytes=0, staging_bytes=0, retain_log=0, log_bytes=0,
-                 drain_host=0):
+                 drain_host=0, fold_on_device=0):
         self.lib = load()
         opts = GraEngineOpts()
         self.lib.gra_engine_opts_init(C.byref(opts))
@@ -303,6 +304,7 @@ class Engine:
         opts.store_ring = store_ring
         opts.retain_log = retain_log
         opts.drain_host = drain_host
+        opts.fold_on_device = fold_on_device
         if log_bytes:
             opts.log_bytes = log_bytes
         if store_bytes:
@@ -403,13 +405,9 @@ class Db:
             raise RuntimeError(f"gra_get rc={rc}: {last_error(self.lib)}")
         return buf.raw[: vlen.value]
 
-    def multiget(self, keys, val_stride=4096):
-        """Batched point reads served from the device store (one block per
-        query); merge-folding queries transparently fall back to the host
-        path. Returns a list of values (None = miss)."""
+    def _multiget(self, keys, val_stride):
+        """gra_multiget as the C ABI answers it -> (out, raw valbuf)."""
         nq = len(keys)
-        if nq == 0:
-            return []
         keybuf = b"".join(keys)
         refs = (GraKeyRef * nq)()
         off = 0
@@ -422,7 +420,33 @@ class Db:
                                    valbuf, val_stride, out)
         if rc != GRA_OK:
             raise RuntimeError(f"gra_multiget rc={rc}: {last_error(self.lib)}")
-        raw = valbuf.raw  # one copy; per-slice .raw would copy 2.5MB each
+        return out, valbuf.raw  # one copy; per-slice .raw would copy 2.5MB each
+
+    def multiget_raw(self, keys, val_stride=4096):
+        """gra_multiget with the statuses the C ABI wrote and no host
+        fallback: [(status, vlen, bytes)], bytes = the min(vlen, val_stride)
+        copied value bytes (b"" unless GRA_GET_FOUND). Shows who served
+        what: GRA_GET_NEEDS_HOST entries are the ones multiget() answers
+        with get()."""
+        if not keys:
+            return []
+        out, raw = self._multiget(keys, val_stride)
+        res = []
+        for i in range(len(keys)):
+            st, vlen = out[i].status, out[i].vlen
+            n = min(vlen, val_stride) if st == GRA_GET_FOUND else 0
+            res.append((st, vlen, raw[i * val_stride:i * val_stride + n]))
+        return res
+
+    def multiget(self, keys, val_stride=4096):
+        """Batched point reads served from the device store; queries the
+        device reports as needing a host fold (live merge operands without
+        fold_on_device, host-origin runs) transparently fall back to get().
+        Returns a list of values (None = miss)."""
+        nq = len(keys)
+        if nq == 0:
+            return []
+        out, raw = self._multiget(keys, val_stride)
         res = []
         for i in range(nq):
             st = out[i].status
@@ -435,14 +459,11 @@ class Db:
                 res.append(self.get(keys[i]))
         return res
 
-    def scan_page(self, lo=b"", hi=None, max_entries=1024, cap=1 << 20):
-        """One page of an ordered range scan over [lo, hi) of the STORED
-        keys (cf keys are [cf LE4 | key]); hi=None is unbounded. Served
-        from the device store when the shard is device-resident; keys whose
-        newest entry is a live Merge are folded here with get(). Returns
-        ([(key, value)], info); info.more says whether the range continues
-        (resume with lo = last key + b"\\x00"). Raises BufferError when the
-        first entry alone exceeds cap."""
+    def scan_page_raw(self, lo=b"", hi=None, max_entries=1024, cap=1 << 20):
+        """One gra_scan page with the statuses the C ABI wrote and no host
+        fallback: ([(key, value_or_None, status)], info); value is None
+        unless status is GRA_GET_FOUND. Raises BufferError when the first
+        entry alone exceeds cap."""
         ents = (GraScanEntry * max(1, max_entries))()
         buf = C.create_string_buffer(max(1, cap))
         info = GraScanInfo()
@@ -458,11 +479,24 @@ class Db:
         for i in range(info.n):
             e = ents[i]
             k = raw[e.key_off:e.key_off + e.key_len]
-            if e.status == GRA_GET_FOUND:
-                res.append((k, raw[e.val_off:e.val_off + e.val_len]))
-            else:  # live merge operands: host fold
-                res.append((k, self.get(k)))
+            v = (raw[e.val_off:e.val_off + e.val_len]
+                 if e.status == GRA_GET_FOUND else None)
+            res.append((k, v, e.status))
         return res, info
+
+    def scan_page(self, lo=b"", hi=None, max_entries=1024, cap=1 << 20):
+        """One page of an ordered range scan over [lo, hi) of the STORED
+        keys (cf keys are [cf LE4 | key]); hi=None is unbounded. Served
+        from the device store when the shard is device-resident; keys the
+        device reports as live merge chains it did not fold (see
+        fold_on_device) are folded here with get(). Returns
+        ([(key, value)], info); info.more says whether the range continues
+        (resume with lo = last key + b"\\x00"). Raises BufferError when the
+        first entry alone exceeds cap."""
+        raw, info = self.scan_page_raw(lo, hi, max_entries, cap)
+        # live merge operands the device left alone: host fold
+        return [(k, v if st == GRA_GET_FOUND else self.get(k))
+                for k, v, st in raw], info
 
     def scan(self, lo=b"", hi=None, limit=None, max_entries=1024,
              cap=1 << 20):
