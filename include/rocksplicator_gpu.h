@@ -173,8 +173,11 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
  * them by (key, seq desc), resolve each key from its newest entry and the
  * covering range tombstones, prefix-sum and emit — all on the GPU; only the
  * emitted bytes cross PCIe. Runs are unsorted by key, so the work per call is
- * O(entries in the shard) WHATEVER THE RANGE (a sorted-run index is future
- * work).
+ * O(entries in the shard) WHATEVER THE RANGE — with one exception: the sorted
+ * run gra_compact leaves as the shard's oldest is entered by a lower-bound
+ * search and contributes only its entries inside [lo, hi). Such a call reports
+ * served_by = GRA_SCAN_DEVICE_INDEXED; runs appended since are still read
+ * whole.
  *
  * Merge operands on the device path (terms as for gra_multiget):
  *   fold_on_device = 0 (default): a key whose newest entry is a live Merge
@@ -201,7 +204,7 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
  * GRA_OK; resume with lo = last key + "\x00". GRA_BUF_TOO_SMALL when the very
  * first entry does not fit. Call gra_flush first for linearizable results;
  * scanning recycled ring-store regions is undefined, as for gra_get. */
-enum { GRA_SCAN_DEVICE = 0, GRA_SCAN_HOST = 1 };
+enum { GRA_SCAN_DEVICE = 0, GRA_SCAN_HOST = 1, GRA_SCAN_DEVICE_INDEXED = 2 };
 typedef struct {
   uint32_t key_off, key_len;  /* stored key bytes, in buf */
   uint32_t val_off, val_len;  /* value bytes, in buf (FOUND only; else 0,0) */
@@ -218,6 +221,58 @@ typedef struct {
 int gra_scan(GraDb *db, const void *lo, size_t lo_len, const void *hi,
              size_t hi_len, uint32_t max_entries, GraScanEntry *out,
              uint8_t *buf, size_t cap, GraScanInfo *info);
+
+/* Compact the shard's device runs ≅ AdminHandler::async_tm_compactDB
+ * (rocksdb_admin/admin_handler.cpp:2160-2175), which calls
+ * ApplicationDB::CompactRange(nullptr, nullptr) (application_db.cpp:138-143):
+ * the longest leading stretch of the shard's run list (oldest first) that is
+ * device-resident — the prefix — is replaced by ONE run that is sorted by
+ * key. Call gra_flush first to include everything submitted; runs appended
+ * while the call works stay behind the new run.
+ *
+ * The new run holds one Put per key gra_get would find looking at the prefix
+ * alone, in ascending bytewise order of the stored key (gra_scan's order).
+ * A key whose newest entry is a live Put keeps that Put's value and seq; a
+ * key with live merge operands is folded with the engine's merge operator,
+ * whatever fold_on_device says, exactly as gra_get folds (floor = max(T, RD),
+ * the operands above it, over T's value iff T is a Put above RD; chains of
+ * any length) and stored as a Put carrying the newest operand's seq.
+ * Deletes, SingleDeletes, range tombstones, shadowed versions and dead keys
+ * are dropped. Seqs grow along the run list, so everything a tombstone,
+ * Delete or Merge of the prefix can act on is in the prefix: no gra_get,
+ * gra_multiget or gra_scan result changes, whatever newer runs follow. The
+ * shard checksum does change: it sums the records the store holds.
+ *
+ * The run is laid out exactly as the apply path lays out a tick (headers,
+ * then 16-B aligned records), with every header's key fingerprint filled,
+ * so all readers work on it unchanged; gra_scan additionally enters it by
+ * a lower-bound search (GRA_SCAN_DEVICE_INDEXED).
+ *
+ * info->status:
+ *   GRA_COMPACT_DONE         prefix replaced;
+ *   GRA_COMPACT_NOTHING      no device-resident prefix (leader-written,
+ *                            drained or empty shard), or the prefix is one
+ *                            already-sorted run; store untouched;
+ *   GRA_COMPACT_UNSUPPORTED  the prefix holds more than 4096 range
+ *                            tombstones or more than 2^30 entries, its
+ *                            output payload would reach 4 GiB, or one value
+ *                            would reach 0xFFFF0000 bytes; store untouched.
+ * Returns GRA_OK with one of these, GRA_ERR on a store_ring engine (it keeps
+ * no runs), or GRA_FULL when the arena cannot hold the output; the store is
+ * untouched then too. LIMIT: the arena is a bump allocator, so the space of
+ * the replaced runs is NOT reclaimed — a compaction needs room for its
+ * output on top of its input. bytes_in / bytes_out (header + payload bytes)
+ * say what a later reclaim would free. */
+enum { GRA_COMPACT_DONE = 0, GRA_COMPACT_NOTHING = 1, GRA_COMPACT_UNSUPPORTED = 2 };
+typedef struct {
+  uint32_t status;               /* GRA_COMPACT_* */
+  uint32_t runs_in, runs_after;  /* runs replaced (0 unless DONE); runs the
+                                    shard holds after the call */
+  uint32_t _pad;
+  uint64_t entries_in, entries_out; /* records in the prefix; records written */
+  uint64_t bytes_in, bytes_out;  /* header + payload bytes, in and out */
+} GraCompactInfo;
+int gra_compact(GraDb *db, GraCompactInfo *info);
 
 /* Full-store content checksum for any-size parity ("checksum of
  * checksums"): per record FNV-1a over (seq LE8 | type | key_len LE4 |

@@ -20,6 +20,12 @@ from .ffi import (  # noqa: F401
     GRA_NO_GPU,
     GRA_SCAN_DEVICE,
     GRA_SCAN_HOST,
+    GRA_SCAN_DEVICE_INDEXED,
+    GRA_COMPACT_DONE,
+    GRA_COMPACT_NOTHING,
+    GRA_COMPACT_UNSUPPORTED,
+    GraCompactInfo,
+    StoreFullError,
     MERGE_CONCAT,
     MERGE_U64ADD,
 )

@@ -323,7 +323,8 @@ __global__ void k_emit(const uint8_t *__restrict__ blobs,
 
 /* G-lane-group cooperative byte copy, dword funnel for misaligned sources
  * (the arenas are over-allocated by 16 B so the +1 word read never faults).
- * Used by the range-scan emit (scan_kernels.h). */
+ * Used by the range-scan emit (scan_kernels.h) and the compaction emit
+ * (compact_kernels.h). */
 template <int G>
 __device__ __forceinline__ void copy_dword(uint8_t *dst, const uint8_t *src,
                                            uint32_t n, uint32_t lane) {
@@ -865,6 +866,9 @@ __global__ void k_mg_emit(const uint8_t *__restrict__ store,
 /* ---------------- device range scan (gra_scan) ---------------- */
 #include "scan_kernels.h"
 
+/* ---------------- device run compaction (gra_compact) ---------------- */
+#include "compact_kernels.h"
+
 /* ---- full-store checksum (parity at any size) ----
  * Same record hash as the oracle's orc_shard_checksum: FNV-1a over
  * (seq LE8 | type | key_len LE4 | val_len LE4 | key | val), u64-ADD
@@ -1125,6 +1129,8 @@ struct GraEngine {
     GraScanEntry *d_ents = nullptr;
     ScCtl *d_ctl = nullptr;
     ScCtl *h_ctl = nullptr; /* pinned mirror */
+    CpCtl *d_cp = nullptr;  /* gra_compact's result block */
+    CpCtl *h_cp = nullptr;  /* pinned mirror */
     size_t runs_cap = 0, bounds_cap = 0, out_cap = 0, cands_cap = 0,
            tombs_cap = 0, items_cap = 0, bsums_cap = 0, ents_cap = 0,
            heads_cap = 0, folds_cap = 0;
@@ -1383,9 +1389,10 @@ GraEngine::~GraEngine() {
   for (void *p : {(void *)sc.d_runs, (void *)sc.d_bounds, (void *)sc.d_out,
                   (void *)sc.d_cands, (void *)sc.d_tombs, (void *)sc.d_items,
                   (void *)sc.d_bsums, (void *)sc.d_ents, (void *)sc.d_ctl,
-                  (void *)sc.d_heads, (void *)sc.d_folds})
+                  (void *)sc.d_heads, (void *)sc.d_folds, (void *)sc.d_cp})
     if (p) (void)hipFree(p);
   if (sc.h_ctl) (void)hipHostFree(sc.h_ctl);
+  if (sc.h_cp) (void)hipHostFree(sc.h_cp);
   for (int i = 0; i < 2; i++) {
     if (d_stage_blobs_bufs[i]) (void)hipFree(d_stage_blobs_bufs[i]);
     if (d_stage_descs_bufs[i]) (void)hipFree(d_stage_descs_bufs[i]);
@@ -2594,7 +2601,8 @@ enum { kScanTakeHostPath = 100 }; /* scan_device: not servable on device */
  * GRA_ERR, or kScanTakeHostPath when the tombstone list overflows or staging
  * cannot be allocated. */
 static int scan_device(GraEngine *e, const std::vector<RunView> &views,
-                       uint64_t total_payload, const uint8_t *lo, uint32_t lo_len, const uint8_t *hi,
+                       bool sorted0, uint64_t total_payload, const uint8_t *lo,
+                       uint32_t lo_len, const uint8_t *hi,
                        uint32_t hi_len, bool has_hi, uint32_t max_entries,
                        GraScanEntry *out, uint8_t *buf, size_t cap,
                        GraScanInfo *info) {
@@ -2698,7 +2706,8 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
         break;
       hipLaunchKernelGGL(k_sc_collect, dim3(bx, (uint32_t)views.size()),
                          dim3(256), 0, st, store, sc.d_runs, bd, sc.d_cands,
-                         cand_cap, sc.d_tombs, kScTombCap, sc.d_ctl);
+                         cand_cap, sc.d_tombs, kScTombCap, sc.d_ctl,
+                         sorted0 ? 1u : 0u);
       /* bitonic sort, sized for the capacity: stages past the padded
        * candidate count return at once */
       hipLaunchKernelGGL(k_sc_sort_tile, dim3(cand_cap / kScTile),
@@ -2804,15 +2813,16 @@ int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
   if (!has_hi) hi_len = 0;
   memset(info, 0, sizeof(*info));
   info->served_by = GRA_SCAN_DEVICE;
-  if (has_hi) { /* lo >= hi: empty range */
+  bool empty_range = false;
+  if (has_hi) { /* lo >= hi */
     size_t m = lo_len < hi_len ? lo_len : hi_len;
     int c = m ? memcmp(lo, hi, m) : 0;
-    if (c > 0 || (c == 0 && lo_len >= hi_len)) return GRA_OK;
+    empty_range = c > 0 || (c == 0 && lo_len >= hi_len);
   }
   /* snapshot the run list, as gra_multiget does */
   std::vector<RunView> views;
   std::vector<std::shared_ptr<Run>> runs;
-  bool any_host = false;
+  bool any_host = false, sorted0 = false;
   uint64_t dev_payload = 0;
   {
     std::lock_guard<std::mutex> lk(ss.mu);
@@ -2822,20 +2832,26 @@ int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
       if (rp->hdr_cur == UINT64_MAX)
         any_host = true;
       else {
+        /* at most one sorted run, and it is the shard's oldest */
+        if (views.empty() && rp->sorted) sorted0 = true;
         views.push_back({rp->hdr_cur, rp->payload_cur, rp->n_entries,
                          rp->pay_rel_base});
         dev_payload += rp->payload_bytes;
       }
     }
   }
-  if (runs.empty()) return GRA_OK;
-  if (!any_host && views.size() <= 65535) { /* grid.y = one row per run */
+  /* a shard whose device path would enter a sorted run says so for every
+   * range, the empty one included */
+  const bool device_ok = !any_host && views.size() <= 65535;
+  if (device_ok && sorted0) info->served_by = GRA_SCAN_DEVICE_INDEXED;
+  if (runs.empty() || empty_range) return GRA_OK;
+  if (device_ok) { /* grid.y = one row per run */
     /* a stored key is shorter than kScMaxBound, so a longer bound orders
      * against every key exactly as its first kScMaxBound bytes do */
     uint32_t l32 = lo_len < kScMaxBound ? (uint32_t)lo_len : kScMaxBound;
     uint32_t h32 = hi_len < kScMaxBound ? (uint32_t)hi_len : kScMaxBound;
-    int rc = scan_device(e, views, dev_payload, lo, l32, hi, h32, has_hi, max_entries, out,
-                         buf, cap, info);
+    int rc = scan_device(e, views, sorted0, dev_payload, lo, l32, hi, h32,
+                         has_hi, max_entries, out, buf, cap, info);
     if (rc != kScanTakeHostPath) return rc;
   }
   /* host path: host-origin runs in the shard (leader writes, drained
@@ -2861,6 +2877,232 @@ int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
   info->n = (uint32_t)res.items.size();
   info->more = res.more ? 1 : 0;
   info->buf_used = res.buf.size();
+  return GRA_OK;
+}
+
+/* ---- gra_compact: the shard's oldest device runs -> one sorted run
+ * (≅ AdminHandler::async_tm_compactDB -> ApplicationDB::CompactRange) ---- */
+
+/* The device chain over `views` (the prefix, oldest first): the scan chain
+ * over the unbounded range with every merge chain folded, then
+ * compact_kernels.h. The candidate buffers are sized up front from the
+ * prefix's entry count, so there is no regrow pass; one D2H of the result
+ * block and one sync. Returns GRA_OK with *res filled, or GRA_ERR. */
+static int compact_device(GraEngine *e, const std::vector<RunView> &views,
+                          bool sorted0, uint64_t total_entries, CpCtl *res) {
+  std::lock_guard<std::mutex> lk_engine(e->mu);
+  auto &sc = e->sc;
+  auto grow = [](auto **p, size_t *have, size_t need) {
+    if (*have >= need) return true;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc(p, need) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    *have = need;
+    return true;
+  };
+  const int mode = e->opts.merge_op == GRA_MERGE_U64ADD ? 2 : 1;
+  uint32_t cap = kScTile; /* power of two >= the prefix's entries */
+  while (cap < total_entries) cap <<= 1;
+  uint32_t nblocks = cap / 256;
+  uint64_t max_run = 0;
+  for (const auto &v : views)
+    max_run = v.n_entries > max_run ? v.n_entries : max_run;
+  uint32_t bx = (uint32_t)((max_run + 255) / 256);
+  if (bx > 1024) bx = 1024;
+  if (bx == 0) bx = 1;
+  bool ok = true;
+  if (!sc.d_ctl) {
+    ok = hipMalloc(&sc.d_ctl, sizeof(ScCtl)) == hipSuccess;
+    if (ok && hipHostMalloc(&sc.h_ctl, sizeof(ScCtl)) != hipSuccess) {
+      (void)hipFree(sc.d_ctl);
+      sc.h_ctl = nullptr;
+      ok = false;
+    }
+    if (!ok) sc.d_ctl = nullptr;
+  }
+  if (ok && !sc.d_cp) {
+    ok = hipMalloc(&sc.d_cp, sizeof(CpCtl)) == hipSuccess;
+    if (ok && hipHostMalloc(&sc.h_cp, sizeof(CpCtl)) != hipSuccess) {
+      (void)hipFree(sc.d_cp);
+      sc.h_cp = nullptr;
+      ok = false;
+    }
+    if (!ok) sc.d_cp = nullptr;
+  }
+  /* the scan's buffers are shared (both run under e->mu); sc.cand_cap, the
+   * capacity gra_scan sizes its launches by, is left alone */
+  if (!ok || !grow(&sc.d_runs, &sc.runs_cap, views.size() * sizeof(RunView)) ||
+      !grow(&sc.d_bounds, &sc.bounds_cap, 64) ||
+      !grow(&sc.d_tombs, &sc.tombs_cap, (size_t)kScTombCap * sizeof(ScTomb)) ||
+      !grow(&sc.d_cands, &sc.cands_cap, (size_t)cap * sizeof(ScCand)) ||
+      !grow(&sc.d_items, &sc.items_cap, (size_t)cap * sizeof(ScItem)) ||
+      !grow(&sc.d_bsums, &sc.bsums_cap, ((size_t)nblocks + 1) * sizeof(ScSum)) ||
+      !grow(&sc.d_heads, &sc.heads_cap, (size_t)cap * sizeof(ScHead)) ||
+      !grow(&sc.d_folds, &sc.folds_cap, (size_t)cap * sizeof(ScFold))) {
+    (void)hipGetLastError();
+    g_err = "gra_compact: device staging allocation failed";
+    return GRA_ERR;
+  }
+  ScBounds bd = {}; /* the whole key range: lo empty, no hi */
+  bd.lo = bd.hi = sc.d_bounds;
+  uint8_t *store = e->d_store;
+  hipStream_t st = e->stream;
+  ok = false;
+  do {
+    if (hipMemsetAsync(sc.d_ctl, 0, sizeof(ScCtl), st) != hipSuccess ||
+        hipMemsetAsync(sc.d_cp, 0, sizeof(CpCtl), st) != hipSuccess ||
+        hipMemcpyAsync(sc.d_runs, views.data(), views.size() * sizeof(RunView),
+                       hipMemcpyHostToDevice, st) != hipSuccess)
+      break;
+    /* grid.y = one row per run, 65535 rows a launch */
+    for (size_t first = 0; first < views.size(); first += 65535) {
+      size_t rows = views.size() - first < 65535 ? views.size() - first : 65535;
+      hipLaunchKernelGGL(k_sc_collect, dim3(bx, (uint32_t)rows), dim3(256), 0,
+                         st, store, sc.d_runs + first, bd, sc.d_cands, cap,
+                         sc.d_tombs, kScTombCap, sc.d_ctl,
+                         (sorted0 && first == 0) ? 1u : 0u);
+    }
+    hipLaunchKernelGGL(k_sc_sort_tile, dim3(cap / kScTile),
+                       dim3(kScTileThreads), 0, st, store, sc.d_cands, sc.d_ctl,
+                       cap, 2u, kScTile, 1);
+    for (uint32_t k = 2 * kScTile; k != 0 && k <= cap; k <<= 1) {
+      for (uint32_t j = k >> 1; j >= kScTile; j >>= 1)
+        hipLaunchKernelGGL(k_sc_sort_global, dim3(cap / 2 / 256), dim3(256), 0,
+                           st, store, sc.d_cands, sc.d_ctl, cap, j, k);
+      hipLaunchKernelGGL(k_sc_sort_tile, dim3(cap / kScTile),
+                         dim3(kScTileThreads), 0, st, store, sc.d_cands,
+                         sc.d_ctl, cap, k, k, 0);
+    }
+    hipLaunchKernelGGL(k_sc_heads, dim3(nblocks), dim3(256), 0, st, store,
+                       sc.d_cands, sc.d_tombs, sc.d_ctl, cap, kScTombCap,
+                       sc.d_heads, sc.d_folds);
+    uint32_t fb = cap / 4 < kScFoldWaves ? cap / 4 : kScFoldWaves;
+    if (mode == 2)
+      hipLaunchKernelGGL((k_sc_fold<2>), dim3(fb / 4), dim3(256), 0, st, store,
+                         sc.d_cands, sc.d_heads, sc.d_ctl, cap, sc.d_folds);
+    else
+      hipLaunchKernelGGL((k_sc_fold<1, true>), dim3(fb / 4), dim3(256), 0, st,
+                         store, sc.d_cands, sc.d_heads, sc.d_ctl, cap,
+                         sc.d_folds);
+    hipLaunchKernelGGL(k_cp_resolve, dim3(nblocks), dim3(256), 0, st, store,
+                       sc.d_cands, sc.d_tombs, sc.d_ctl, cap, kScTombCap,
+                       sc.d_items, sc.d_bsums, sc.d_folds, sc.d_cp);
+    hipLaunchKernelGGL(k_cp_finish, dim3(1), dim3(256), 0, st, sc.d_bsums,
+                       nblocks, sc.d_ctl, cap, kScTombCap, e->d_cursor,
+                       (uint64_t)e->opts.store_bytes, sc.d_cp);
+    if (mode == 2) {
+      hipLaunchKernelGGL((k_cp_emit<16, 2>), dim3(cap / 16), dim3(256), 0, st,
+                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.d_ctl,
+                         sc.d_cp, cap, sc.d_folds);
+    } else {
+      hipLaunchKernelGGL((k_cp_emit<16, 1>), dim3(cap / 16), dim3(256), 0, st,
+                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.d_ctl,
+                         sc.d_cp, cap, sc.d_folds);
+      hipLaunchKernelGGL(k_cp_emit_chain, dim3(fb / 4), dim3(256), 0, st, store,
+                         sc.d_cands, sc.d_items, sc.d_bsums, sc.d_heads,
+                         sc.d_ctl, sc.d_cp, cap, sc.d_folds);
+    }
+    if (hipGetLastError() != hipSuccess) break;
+    if (hipMemcpyAsync(sc.h_cp, sc.d_cp, sizeof(CpCtl), hipMemcpyDeviceToHost,
+                       st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      break;
+    ok = true;
+  } while (0);
+  if (!ok) {
+    (void)hipStreamSynchronize(st);
+    g_err = "gra_compact: device op failed";
+    return GRA_ERR;
+  }
+  *res = *sc.h_cp;
+  return GRA_OK;
+}
+
+int gra_compact(GraDb *db, GraCompactInfo *info) {
+  if (!db || !info) {
+    g_err = "gra_compact: null argument";
+    return GRA_ERR;
+  }
+  memset(info, 0, sizeof(*info));
+  GraEngine *e = db->e;
+  if (e->opts.store_ring) {
+    g_err = "gra_compact: a store_ring engine keeps no runs";
+    return GRA_ERR;
+  }
+  ShardState &ss = e->shards[db->shard];
+  /* the prefix: the leading device-resident runs, oldest first */
+  std::vector<std::shared_ptr<Run>> snap;
+  {
+    std::lock_guard<std::mutex> lk(ss.mu);
+    for (const auto &rp : ss.runs) {
+      if (rp->hdr_cur == UINT64_MAX) break;
+      snap.push_back(rp);
+    }
+    info->runs_after = (uint32_t)ss.runs.size();
+  }
+  info->status = GRA_COMPACT_NOTHING;
+  if (snap.empty() || (snap.size() == 1 && snap[0]->sorted)) return GRA_OK;
+  std::vector<RunView> views;
+  for (const auto &rp : snap) {
+    if (rp->n_entries == 0) continue;
+    views.push_back(
+        {rp->hdr_cur, rp->payload_cur, rp->n_entries, rp->pay_rel_base});
+    info->entries_in += rp->n_entries;
+    info->bytes_in +=
+        (uint64_t)rp->n_entries * sizeof(wb::RecHdr) + rp->payload_bytes;
+  }
+  if (views.empty()) return GRA_OK;
+  /* range tombstones are counted with the point entries here: the bound is
+   * what the candidate buffers are sized from */
+  if (info->entries_in > (1ull << 30)) {
+    info->status = GRA_COMPACT_UNSUPPORTED;
+    return GRA_OK;
+  }
+  CpCtl cp;
+  int rc = compact_device(e, views, snap[0]->sorted, info->entries_in, &cp);
+  if (rc != GRA_OK) return rc;
+  if (cp.unsupported) {
+    info->status = GRA_COMPACT_UNSUPPORTED;
+    return GRA_OK;
+  }
+  if (cp.overflow) {
+    g_err = "gra_compact: the store arena cannot hold the compacted run";
+    return GRA_FULL;
+  }
+  auto run = std::make_shared<Run>();
+  run->base_seq = snap.front()->base_seq;
+  run->last_seq = snap.back()->last_seq;
+  run->n_entries = cp.n_out;
+  run->payload_bytes = (uint32_t)cp.payload_bytes;
+  run->hdr_cur = cp.hdr_off;
+  run->payload_cur = cp.payload_off;
+  run->pay_rel_base = 0;
+  run->kpref_built = true; /* k_cp_emit filled every header's fingerprint */
+  run->sorted = true;
+  {
+    std::lock_guard<std::mutex> lk(ss.mu);
+    /* runs are only ever appended, so the snapshot is still the head of the
+     * list unless another gra_compact on this shard got there first */
+    bool same = ss.runs.size() >= snap.size();
+    for (size_t i = 0; same && i < snap.size(); i++)
+      same = ss.runs[i] == snap[i];
+    if (!same) {
+      g_err = "gra_compact: the shard's run list changed under the call";
+      return GRA_ERR;
+    }
+    ss.runs.erase(ss.runs.begin(), ss.runs.begin() + snap.size());
+    /* a prefix with no live key leaves no run behind */
+    if (run->n_entries > 0) ss.runs.insert(ss.runs.begin(), std::move(run));
+    info->runs_after = (uint32_t)ss.runs.size();
+  }
+  info->status = GRA_COMPACT_DONE;
+  info->runs_in = (uint32_t)snap.size();
+  info->entries_out = cp.n_out;
+  info->bytes_out = (uint64_t)cp.n_out * sizeof(wb::RecHdr) + cp.payload_bytes;
   return GRA_OK;
 }
 

@@ -146,21 +146,24 @@ void run_probe(const std::vector<std::shared_ptr<Run>> &runs, const void *key_,
   }
 }
 
-int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo_,
-             size_t lo_len, const void *hi_, size_t hi_len, int merge_op,
-             uint32_t max_entries, size_t cap, ScanResult *out) {
-  const uint8_t *lo = (const uint8_t *)lo_, *hi = (const uint8_t *)hi_;
-  out->items.clear();
-  out->buf.clear();
-  out->more = false;
-  if (hi && key_cmp(lo, lo_len, hi, hi_len) >= 0) return 0; /* empty range */
+namespace {
 
-  struct Point {
-    const uint8_t *key, *val;
-    uint64_t seq;
-    uint32_t klen, vlen;
-    uint8_t type;
-  };
+struct Point {
+  const uint8_t *key, *val;
+  uint64_t seq;
+  uint32_t klen, vlen;
+  uint8_t type;
+};
+
+/* The sweep run_scan and run_compact share: every stored key k with
+ * lo <= k < hi that run_get finds, ascending, with its folded value.
+ * visit(head, value) gets the key's newest entry; returning false ends the
+ * sweep. One sort of the in-range point entries by (key asc, seq desc) plus
+ * a sweep over the range tombstones. */
+template <class Visit>
+void sweep_live(const std::vector<std::shared_ptr<Run>> &runs,
+                const uint8_t *lo, size_t lo_len, const uint8_t *hi,
+                size_t hi_len, int merge_op, Visit &&visit) {
   struct Tomb {
     const uint8_t *b, *e;
     uint32_t bl, el;
@@ -224,10 +227,6 @@ int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo_,
     bool live = (head.type == wb::kValue || head.type == wb::kMerge) &&
                 head.seq > rd;
     if (live) {
-      if (out->items.size() >= max_entries) {
-        out->more = true;
-        return 0;
-      }
       /* fold: operands above the newest terminator, all above RD */
       ops.clear();
       const uint8_t *base = nullptr;
@@ -246,22 +245,96 @@ int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo_,
         break;
       }
       fold_value(have_base, base, base_len, ops, merge_op, &val);
-      if (out->buf.size() + head.klen + val.size() > cap) {
-        if (out->items.empty()) return 2;
-        out->more = true;
-        return 0;
-      }
-      ScanItem it;
-      it.key_off = (uint32_t)out->buf.size();
-      it.key_len = head.klen;
-      out->buf.append((const char *)head.key, head.klen);
-      it.val_off = (uint32_t)out->buf.size();
-      it.val_len = (uint32_t)val.size();
-      out->buf.append(val);
-      out->items.push_back(it);
+      if (!visit(head, val)) return;
     }
     i = end;
   }
+}
+
+} /* namespace */
+
+int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo_,
+             size_t lo_len, const void *hi_, size_t hi_len, int merge_op,
+             uint32_t max_entries, size_t cap, ScanResult *out) {
+  const uint8_t *lo = (const uint8_t *)lo_, *hi = (const uint8_t *)hi_;
+  out->items.clear();
+  out->buf.clear();
+  out->more = false;
+  if (hi && key_cmp(lo, lo_len, hi, hi_len) >= 0) return 0; /* empty range */
+  int rc = 0;
+  sweep_live(runs, lo, lo_len, hi, hi_len, merge_op,
+             [&](const Point &head, const std::string &val) {
+               if (out->items.size() >= max_entries) {
+                 out->more = true;
+                 return false;
+               }
+               if (out->buf.size() + head.klen + val.size() > cap) {
+                 if (out->items.empty())
+                   rc = 2;
+                 else
+                   out->more = true;
+                 return false;
+               }
+               ScanItem it;
+               it.key_off = (uint32_t)out->buf.size();
+               it.key_len = head.klen;
+               out->buf.append((const char *)head.key, head.klen);
+               it.val_off = (uint32_t)out->buf.size();
+               it.val_len = (uint32_t)val.size();
+               out->buf.append(val);
+               out->items.push_back(it);
+               return true;
+             });
+  return rc;
+}
+
+int run_compact(const std::vector<std::shared_ptr<Run>> &runs, int merge_op,
+                Run *out) {
+  *out = Run();
+  if (runs.empty()) return 0;
+  uint64_t entries = 0, tombs = 0;
+  for (const auto &rp : runs) {
+    const wb::RecHdr *h = (const wb::RecHdr *)rp->hdrs_data();
+    for (uint32_t i = 0; i < rp->n_entries; i++)
+      tombs += h[i].type == wb::kRangeDeletion;
+    entries += rp->n_entries;
+  }
+  if (tombs > 4096 || entries > (1ull << 30)) return 1;
+  std::vector<wb::RecHdr> hdrs;
+  std::vector<uint8_t> pay;
+  bool too_big = false;
+  sweep_live(runs, nullptr, 0, nullptr, 0, merge_op,
+             [&](const Point &head, const std::string &val) {
+               uint64_t rec = (uint64_t)head.klen + val.size();
+               if (rec >= 0xFFFF0000ull ||
+                   pay.size() + ((rec + 15) & ~15ull) >= (1ull << 32)) {
+                 too_big = true;
+                 return false;
+               }
+               wb::RecHdr h;
+               h.seq = head.seq; /* a folded chain carries its head's seq */
+               h.kv_off = (uint32_t)pay.size(); /* run-relative */
+               h.val_len = (uint32_t)val.size();
+               h.key_len = (uint16_t)head.klen;
+               h.type = wb::kValue;
+               h.flags = 0;
+               h.kpref = wb::key_fnv_fold(wb::kFnvBasis32, head.key, head.klen);
+               hdrs.push_back(h);
+               pay.insert(pay.end(), head.key, head.key + head.klen);
+               pay.insert(pay.end(), val.begin(), val.end());
+               pay.resize((pay.size() + 15) & ~(size_t)15, 0);
+               return true;
+             });
+  if (too_big) return 1;
+  out->base_seq = runs.front()->base_seq;
+  out->last_seq = runs.back()->last_seq;
+  out->n_entries = (uint32_t)hdrs.size();
+  out->payload_bytes = (uint32_t)pay.size();
+  out->hdrs.assign((const uint8_t *)hdrs.data(),
+                   (const uint8_t *)(hdrs.data() + hdrs.size()));
+  out->payload = std::move(pay);
+  out->kpref_built = true;
+  out->sorted = true;
   return 0;
 }
 

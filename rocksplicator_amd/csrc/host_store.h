@@ -45,6 +45,9 @@ struct Run {
   const uint8_t *hdr_p = nullptr, *pay_p = nullptr;
   bool kpref_built = false; /* device read index (k_kpref) done; guarded by
                                the engine mutex at build time */
+  bool sorted = false; /* written by gra_compact / run_compact: one Put per
+                          key, ascending bytewise key order, no tombstones.
+                          A shard holds at most one, as its oldest run */
   const uint8_t *hdrs_data() const { return hdr_p ? hdr_p : hdrs.data(); }
   const uint8_t *payload_data() const { return pay_p ? pay_p : payload.data(); }
   bool resident() const {
@@ -121,6 +124,19 @@ struct ScanResult {
 int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo,
              size_t lo_len, const void *hi, size_t hi_len, int merge_op,
              uint32_t max_entries, size_t cap, ScanResult *out);
+
+/* Compaction of a run list (oldest first) into one sorted run: the plain-C++
+ * statement of what gra_compact's device chain writes, result and layout.
+ * out gets one Put record per key run_get finds over `runs`, in ascending
+ * bytewise key order — a live Put as it stands, a live merge chain folded
+ * with merge_op and carrying its newest operand's seq — in the apply path's
+ * layout: RecHdr array, 16-B aligned and padded records, run-relative kv_off,
+ * flags 0, kpref filled. base_seq / last_seq span the input. Returns 0, or 1
+ * where gra_compact reports GRA_COMPACT_UNSUPPORTED (more than 4096 range
+ * tombstones or 2^30 entries, a payload of 4 GiB, a record of 0xFFFF0000
+ * bytes); out is then empty. */
+int run_compact(const std::vector<std::shared_ptr<Run>> &runs, int merge_op,
+                Run *out);
 
 /* Host apply of one rep blob (leader write path): decodes with wb::walk and
  * builds a Run in the same format the GPU emits. Returns false on corrupt

@@ -22,7 +22,9 @@
  *
  * Every kernel sizes itself from the device-side candidate count, so the
  * host enqueues the whole chain without a sync in between. Work per call is
- * O(entries in the shard), whatever the range. */
+ * O(entries in the shard), whatever the range — except for a shard's sorted
+ * run (gra_compact, compact_kernels.h): k_sc_collect enters it by binary
+ * search and reads only the slice [lo, hi). */
 #pragma once
 
 constexpr uint32_t kScTile = 1024;     /* records per LDS tile: 32 KB */
@@ -157,20 +159,88 @@ __device__ inline uint32_t sc_padded(uint32_t n) {
   return N; /* <= cap: cap is a power of two >= kScTile */
 }
 
+/* first 8 key bytes as ScCand::pref; records are 16-B aligned, so one
+ * aligned load yields them */
+__device__ inline uint64_t sc_key_pref(const uint8_t *k, uint32_t klen) {
+  uint2 w = *(const uint2 *)k;
+  uint64_t pref = __builtin_bswap64((uint64_t)w.x | ((uint64_t)w.y << 32));
+  return klen >= 8 ? pref
+         : klen == 0 ? 0
+                     : pref & (~0ULL << (8 * (8 - klen)));
+}
+
+/* Sorted run (gra_compact: point records only, strictly ascending keys):
+ * index of its first key >= bound, with the collect pass's comparator,
+ * searched by one whole wave. Every step the 64 lanes probe 64 evenly spaced
+ * entries of [lo, hi) and a ballot keeps the one gap the answer lies in, so
+ * the range shrinks 64-fold for two dependent loads (header, then key):
+ * three steps for 100K entries where a binary search takes seventeen. All
+ * 64 lanes must call it; the result is wave-uniform. */
+__device__ inline uint32_t sc_lower_bound(const uint8_t *store,
+                                          const RunView &rv,
+                                          const uint8_t *b, uint32_t bl,
+                                          uint64_t bpref, uint32_t lane) {
+  const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv.hdr_off);
+  uint32_t lo = 0, hi = rv.n_entries;
+  while (lo < hi) { /* wave-uniform */
+    uint32_t step = (hi - lo + 63) / 64;
+    uint64_t p = (uint64_t)lo + (uint64_t)lane * step;
+    bool less = false;
+    if (p < hi) {
+      wb::RecHdr h = hdrs[p];
+      const uint8_t *k = store + rv.payload_off + (h.kv_off - rv.pay_rel_base);
+      uint64_t pref = sc_key_pref(k, h.key_len);
+      less = pref < bpref ||
+             (pref == bpref && sc_key_cmp_from(k, h.key_len, b, bl, 8) < 0);
+    }
+    /* keys ascend, so the lanes that see a smaller key are the leading ones */
+    uint32_t c = (uint32_t)__popcll(__ballot(less));
+    if (c == 0) return lo;
+    /* probe c-1 is below the bound, probe c (if there is one) is not */
+    uint64_t next_hi = (uint64_t)lo + (uint64_t)c * step;
+    lo = lo + (c - 1) * step + 1;
+    if (next_hi < hi) hi = (uint32_t)next_hi;
+  }
+  return lo;
+}
+
+/* sorted0: row 0 of `runs` is the shard's sorted run. Its in-range entries
+ * are the slice between the lower bounds of lo and hi, and it holds no
+ * tombstones, so the block strides over that slice only. */
 __global__ void __launch_bounds__(256) k_sc_collect(
     const uint8_t *__restrict__ store, const RunView *__restrict__ runs,
     ScBounds bd, ScCand *__restrict__ cands, uint32_t cand_cap,
-    ScTomb *__restrict__ tombs, uint32_t tomb_cap, ScCtl *__restrict__ ctl) {
+    ScTomb *__restrict__ tombs, uint32_t tomb_cap, ScCtl *__restrict__ ctl,
+    uint32_t sorted0) {
+  __shared__ uint32_t slice[2];
   RunView rv = runs[blockIdx.y];
   const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv.hdr_off);
   uint32_t lane = threadIdx.x & 63;
+  uint32_t begin = 0, end = rv.n_entries;
+  if (sorted0 && blockIdx.y == 0) { /* block-uniform */
+    uint32_t wave = threadIdx.x >> 6; /* wave 0 finds lo, wave 1 finds hi */
+    if (wave == 0) {
+      uint32_t b = bd.lo_len ? sc_lower_bound(store, rv, bd.lo, bd.lo_len,
+                                              bd.lo_pref, lane)
+                             : 0u;
+      if (lane == 0) slice[0] = b;
+    } else if (wave == 1) {
+      uint32_t e = bd.has_hi ? sc_lower_bound(store, rv, bd.hi, bd.hi_len,
+                                              bd.hi_pref, lane)
+                             : rv.n_entries;
+      if (lane == 0) slice[1] = e;
+    }
+    __syncthreads();
+    begin = slice[0];
+    end = slice[1];
+  }
   /* block-uniform trip count: every lane reaches the ballot below */
-  for (uint32_t base = blockIdx.x * blockDim.x; base < rv.n_entries;
+  for (uint32_t base = begin + blockIdx.x * blockDim.x; base < end;
        base += gridDim.x * blockDim.x) {
     uint32_t i = base + threadIdx.x;
     bool take = false;
     ScCand c = {};
-    if (i < rv.n_entries) {
+    if (i < end) {
       wb::RecHdr h = hdrs[i];
       uint64_t koff = rv.payload_off + (h.kv_off - rv.pay_rel_base);
       const uint8_t *k = store + koff;
@@ -183,15 +253,8 @@ __global__ void __launch_bounds__(256) k_sc_collect(
           if (slot < tomb_cap) tombs[slot] = {h.seq, koff, h.key_len, h.val_len};
         }
       } else {
-        /* records are 16-B aligned: one aligned load yields the key's
-         * first 8 bytes, which decide most entries against both bounds */
-        uint2 w = *(const uint2 *)k;
-        uint64_t pref =
-            __builtin_bswap64((uint64_t)w.x | ((uint64_t)w.y << 32));
-        pref = h.key_len >= 8 ? pref
-               : h.key_len == 0
-                   ? 0
-                   : pref & (~0ULL << (8 * (8 - h.key_len)));
+        /* the key's first 8 bytes decide most entries against both bounds */
+        uint64_t pref = sc_key_pref(k, h.key_len);
         bool ge_lo =
             pref > bd.lo_pref ||
             (pref == bd.lo_pref &&
@@ -364,7 +427,7 @@ struct ScFoldAcc {
 };
 
 /* U x 64 successors from pos; true when the chain ended (wave-uniform) */
-template <int MODE, int U>
+template <int MODE, int U, bool UNBOUNDED>
 __device__ __forceinline__ bool sc_fold_step(
     const uint8_t *__restrict__ store, const ScCand *__restrict__ cands,
     uint32_t n, const ScCand &hc, const ScHead &hd, uint32_t pos,
@@ -399,7 +462,7 @@ __device__ __forceinline__ bool sc_fold_step(
       a.base = 1;
     }
     if (stop) return true;
-    if (MODE == 1 &&
+    if (MODE == 1 && !UNBOUNDED &&
         pos - hd.idx + (u + 1) * 64 > fold::kFoldMaxConcatOps) {
       a.over = true;
       return true;
@@ -408,7 +471,10 @@ __device__ __forceinline__ bool sc_fold_step(
   return false;
 }
 
-template <int MODE>
+/* UNBOUNDED (gra_compact, MODE 1): a concat chain of any length folds; its
+ * operand count goes to ScFold::sum, which concat leaves free, instead of
+ * the 24 flag bits. */
+template <int MODE, bool UNBOUNDED = false>
 __global__ void __launch_bounds__(256) k_sc_fold(
     const uint8_t *__restrict__ store, const ScCand *__restrict__ cands,
     const ScHead *__restrict__ heads, const ScCtl *__restrict__ ctl,
@@ -422,9 +488,11 @@ __global__ void __launch_bounds__(256) k_sc_fold(
     ScHead hd = heads[h];
     ScCand hc = cands[hd.idx];
     ScFoldAcc a = {0, 0, 0, false};
-    bool done = sc_fold_step<MODE, 1>(store, cands, n, hc, hd, hd.idx, lane, a);
+    bool done = sc_fold_step<MODE, 1, UNBOUNDED>(store, cands, n, hc, hd,
+                                                 hd.idx, lane, a);
     for (uint32_t pos = hd.idx + 64; !done; pos += 256)
-      done = sc_fold_step<MODE, 4>(store, cands, n, hc, hd, pos, lane, a);
+      done = sc_fold_step<MODE, 4, UNBOUNDED>(store, cands, n, hc, hd, pos,
+                                              lane, a);
     bool over = a.over;
     uint64_t acc = sc_wave_sum(a.acc);
     uint32_t nops = (uint32_t)sc_wave_sum(a.cnt);
@@ -435,12 +503,14 @@ __global__ void __launch_bounds__(256) k_sc_fold(
         f.sum = acc;
         f.vlen = 8;
         f.flags |= kScFoldFolded;
-      } else if (!over && nops <= fold::kFoldMaxConcatOps) {
+      } else if (UNBOUNDED || (!over && nops <= fold::kFoldMaxConcatOps)) {
         /* acc already holds the base's bytes along with the operands' */
         uint64_t len = fold::concat_len(has_base != 0, 0, acc, nops);
         if (len + hc.klen < 0xFFFF0000ull) { /* ScItem.cost is 32 bits */
           f.vlen = (uint32_t)len;
-          f.flags |= kScFoldFolded | (has_base ? kScFoldBase : 0) | (nops << 8);
+          f.flags |= kScFoldFolded | (has_base ? kScFoldBase : 0) |
+                     (UNBOUNDED ? 0u : nops << 8);
+          if (UNBOUNDED) f.sum = nops;
         }
       }
       folds[hd.idx] = f;

@@ -237,7 +237,8 @@ struct RecHdr {
   uint32_t val_len;
   uint16_t key_len;  /* includes 4-byte cf prefix when cf_id != 0 */
   uint8_t type;      /* base tag */
-  uint8_t flags;     /* bit0: cf-prefixed key */
+  uint8_t flags;     /* bit0: cf-prefixed key. Written by the apply paths,
+                        read by none; gra_compact writes 0 */
   uint32_t kpref;    /* first min(4,key_len) key bytes, zero-padded — lets
                         point lookups filter without touching the payload */
 };

@@ -53,6 +53,28 @@ GRA_GET_NEEDS_HOST = 2
 
 GRA_SCAN_DEVICE = 0
 GRA_SCAN_HOST = 1
+GRA_SCAN_DEVICE_INDEXED = 2
+
+GRA_COMPACT_DONE = 0
+GRA_COMPACT_NOTHING = 1
+GRA_COMPACT_UNSUPPORTED = 2
+
+
+class StoreFullError(RuntimeError):
+    """GRA_FULL: the device run arena cannot hold what the call writes."""
+
+
+class GraCompactInfo(C.Structure):
+    _fields_ = [
+        ("status", C.c_uint32),
+        ("runs_in", C.c_uint32),
+        ("runs_after", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("entries_in", C.c_uint64),
+        ("entries_out", C.c_uint64),
+        ("bytes_in", C.c_uint64),
+        ("bytes_out", C.c_uint64),
+    ]
 
 
 class GraScanEntry(C.Structure):
@@ -168,6 +190,7 @@ def load():
     lib.gra_scan.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p,
                              C.c_size_t, C.c_uint32, C.POINTER(GraScanEntry),
                              C.c_char_p, C.c_size_t, C.POINTER(GraScanInfo)]
+    lib.gra_compact.argtypes = [C.c_void_p, C.POINTER(GraCompactInfo)]
     lib.gra_shard_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.gra_pin_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8))]
     lib.gra_pin_free.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
@@ -512,6 +535,22 @@ class Db:
             if left is not None:
                 left -= len(ents)
             lo = ents[-1][0] + b"\x00"
+
+    def compact(self):
+        """gra_compact: replace the shard's leading device-resident runs by
+        one key-sorted run (one Put per live key, merge chains folded).
+        Call Engine.flush() first to include everything submitted. Returns
+        the GraCompactInfo; info.status is GRA_COMPACT_DONE, _NOTHING or
+        _UNSUPPORTED. Raises StoreFullError when the arena cannot hold the
+        output and RuntimeError on a store_ring engine; the store is
+        untouched in both cases."""
+        info = GraCompactInfo()
+        rc = self.lib.gra_compact(self.h, C.byref(info))
+        if rc == GRA_FULL:
+            raise StoreFullError(f"gra_compact: {last_error(self.lib)}")
+        if rc != GRA_OK:
+            raise RuntimeError(f"gra_compact rc={rc}: {last_error(self.lib)}")
+        return info
 
     def checksum(self):
         """Order-independent full-store content checksum (device-computed;

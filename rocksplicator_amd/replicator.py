@@ -123,6 +123,15 @@ class Replicator:
         if role in (FOLLOWER, OBSERVER) and upstream_db is not None:
             self._start_pull(rs)
 
+    # ≅ AdminHandler::async_tm_compactDB (admin_handler.cpp:2160-2175 ->
+    # ApplicationDB::CompactRange(nullptr, nullptr)): flush, then replace
+    # the shard's device runs by one key-sorted run. Any role; a LEADER's
+    # host-written runs are not device-resident and stay as they are.
+    def compact_db(self, name):
+        rs = self.get(name)
+        self.engine.flush()
+        return rs.db.compact()
+
     # ≅ RocksDBReplicator::write -> ReplicatedDB::Write
     # (replicated_db.cpp:103-166)
     def write(self, name, rep_bytes, mode=0):
