@@ -32,7 +32,7 @@ oracle/libwb_oracle.so: oracle/wb_oracle.c oracle/wb_oracle.h
 
 # auxiliary binaries (C++ chain test, streaming bench, kernel microbenches,
 # DbWrapper-adapter compile proof)
-tools: build/test_cpp_chain build/bench_stream build/micro_copy build/micro_snappy build/seam_compile_check
+tools: build/test_cpp_chain build/bench_stream build/micro_copy build/micro_snappy build/micro_decode build/seam_compile_check
 
 # compile-proof of INTEGRATION.md's GpuApplyDbWrapper against the exact
 # DbWrapper virtual seam (mock restatement of db_wrapper.h:6-15); plain g++
@@ -51,6 +51,9 @@ build/micro_copy: scripts/micro_copy.hip $(CSRC)/part_copy.h | build
 	$(HIPCC) $(HIPFLAGS) -x hip $< -o $@
 
 build/micro_snappy: scripts/micro_snappy.hip | build
+	$(HIPCC) $(HIPFLAGS) -x hip $< -o $@
+
+build/micro_decode: scripts/micro_decode.hip $(CSRC)/wb_format.h | build
 	$(HIPCC) $(HIPFLAGS) -x hip $< -o $@
 
 clean:

@@ -172,22 +172,58 @@ __device__ __forceinline__ uint2 block_scan256(uint2 v, uint2 *total) {
   return make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
 }
 
-__global__ void k_decode(const uint8_t *__restrict__ blobs,
-                         const UpdDesc *__restrict__ descs, uint32_t n,
-                         wb::WalkTotals *__restrict__ totals, uint32_t max_rec,
-                         uint32_t *__restrict__ err_ring, uint32_t tick,
-                         uint2 *__restrict__ partial, uint2 *__restrict__ bsums,
-                         wb::Rec *__restrict__ reccache,
-                         uint8_t *__restrict__ ok_out) {
+/* The walk is a chain of dependent byte loads (header, tag, length varints),
+ * each a fully divergent wave load when it goes to global memory. So each
+ * lane first stages the head of its blob into its own LDS row with
+ * independent 16 B loads (as k_snappy does; +4 B row pad for the same bank
+ * reason, no cross-lane sharing, no barrier) and parses from there: the
+ * chain to global memory is the desc, then one batch of wide loads. A walk
+ * that leaves the window (long keys, multi-record batches) reads on from
+ * the blob. Chunk loads start at the blob's first byte, unaligned, and stop
+ * at the chunk that holds its last byte (wb::win_chunks): at most 15 B past
+ * the blob, inside the 16 B every blob arena is over-allocated by. */
+constexpr uint32_t kDecodeWin = 48; /* 256 x (48+4) = 13 KiB LDS per block;
+                                       48 covers header, tag, a 5 B cf id and
+                                       the length varints around a key of up
+                                       to 27 B. 64 ties on plain puts and
+                                       loses 15 % on cf puts, 128 loses
+                                       everywhere (scripts/micro_decode.hip,
+                                       profiles/decodewin) */
+static_assert(kDecodeWin % 16 == 0, "window is staged in 16 B chunks");
+
+__global__ void __launch_bounds__(256) k_decode(
+    const uint8_t *__restrict__ blobs, const UpdDesc *__restrict__ descs,
+    uint32_t n, wb::WalkTotals *__restrict__ totals, uint32_t max_rec,
+    uint32_t *__restrict__ err_ring, uint32_t tick,
+    uint2 *__restrict__ partial, uint2 *__restrict__ bsums,
+    wb::Rec *__restrict__ reccache, uint8_t *__restrict__ ok_out) {
+  __shared__ uint32_t stage[256 * (kDecodeWin + 4) / 4];
   uint32_t i = blockIdx.x * 256 + threadIdx.x;
   uint2 v = make_uint2(0, 0);
   if (i < n) {
     UpdDesc d = descs[i];
+    const uint8_t *rep = blobs + d.off;
+    uint32_t *row = stage + threadIdx.x * ((kDecodeWin + 4) / 4);
+    const uint32_t nch = wb::win_chunks(d.len, kDecodeWin);
+    uint4 c[kDecodeWin / 16];
+#pragma unroll
+    for (uint32_t k = 0; k < kDecodeWin / 16; k++)
+      if (k < nch) c[k] = *(const uint4 *)(rep + 16 * k);
+#pragma unroll
+    for (uint32_t k = 0; k < kDecodeWin / 16; k++)
+      if (k < nch) { /* rows are 4 B aligned: dword stores */
+        row[4 * k + 0] = c[k].x;
+        row[4 * k + 1] = c[k].y;
+        row[4 * k + 2] = c[k].z;
+        row[4 * k + 3] = c[k].w;
+      }
+    wb::WinSrc src = {(const uint8_t *)row, wb::win_bytes(d.len, kDecodeWin),
+                      rep};
     wb::Rec *cache = reccache + (size_t)i * kRecCache;
-    wb::WalkTotals t = wb::walk_f(blobs + d.off, d.len,
-                                  [&](const wb::Rec &r, uint32_t idx) {
-                                    if (idx < kRecCache) cache[idx] = r;
-                                  });
+    wb::WalkTotals t = wb::walk_src(src, d.len,
+                                    [&](const wb::Rec &r, uint32_t idx) {
+                                      if (idx < kRecCache) cache[idx] = r;
+                                    });
     if (t.n_records > max_rec) t.ok = 0;
     totals[i] = t;
     ok_out[i] = (uint8_t)t.ok;
@@ -998,7 +1034,7 @@ struct Slot {
   DevRunDesc *d_rundescs = nullptr; /* per-slot device buffer so the D2H can
                                        overlap the next tick's kernels */
   uint8_t *d_ok = nullptr;         /* per-update validity from k_decode */
-  uint8_t *h_ok = nullptr;         /* pinned mirror (read only on error) */
+  uint8_t *h_ok = nullptr;         /* pinned mirror (fetched only on error) */
   uint32_t *h_err = nullptr;
   UpdDesc *h_descs = nullptr;      /* staging-path desc upload */
   bool busy = false;
@@ -1585,7 +1621,8 @@ int GraEngine::enqueue_tick(TickInput &in) {
                          hipMemcpyDeviceToHost, copyout));
   HIP_TRY(hipMemcpyAsync(sl.h_err, d_err_ring + (tick % kErrRing), 4,
                          hipMemcpyDeviceToHost, copyout));
-  HIP_TRY(hipMemcpyAsync(sl.h_ok, sl.d_ok, n, hipMemcpyDeviceToHost, copyout));
+  /* sl.d_ok stays on the device: ingest_one fetches it only when the tick
+   * reported an error */
   HIP_TRY(hipMemcpyAsync(sl.h_place, place_slot, sizeof(TickPlace),
                          hipMemcpyDeviceToHost, copyout));
   if (opts.drain_host && !t.counts.empty()) {
@@ -1706,14 +1743,18 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
     return true;
   };
   if (err != 0) {
-    /* Precise corruption recovery: per-update validity came back with the
-     * run descriptors (sl.h_ok). Per shard, keep the prefix of records from
-     * updates BEFORE its first corrupt one (their seqs are final), drop the
+    /* Precise corruption recovery: fetch the per-update validity now (the
+     * slot and its d_ok belong to this tick until ingest returns, and the
+     * tick's kernels have retired, so a blocking copy reads its bytes; the
+     * clean path never pays for the download). Per shard, keep the prefix
+     * of records from updates BEFORE its first corrupt one (their seqs are
+     * final), drop the
      * rest (their host-assigned seqs assumed the corrupt batch applied),
      * roll the shard's seq back to the kept boundary and poison it — the
      * reference's failed-apply -> re-pull-from-LatestSequenceNumber cadence
      * (replicated_db.cpp:378-382). Groups are in tick order, so a later
      * group of an already-poisoned shard is dropped whole. */
+    HIP_TRY(hipMemcpy(sl.h_ok, sl.d_ok, t.n, hipMemcpyDeviceToHost));
     const bool have_counts = t.counts.size() == t.n;
     for (uint32_t g = 0; g < t.ngroups; g++) {
       DevRunDesc &rd = sl.h_rundescs[g];

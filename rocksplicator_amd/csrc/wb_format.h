@@ -61,14 +61,60 @@ WB_HD uint32_t fixed32_le(const uint8_t *p) {
 #endif
 }
 
-/* varint32 decode; returns bytes consumed (1..5), 0 on error/overrun.
- * p must have at least `avail` readable bytes. */
-WB_HD uint32_t varint32(const uint8_t *p, uint32_t avail, uint32_t *out) {
+/* ---- byte sources: where the parser's bytes come from ----
+ * A source answers byte(pos), u32(pos) and u64(pos) for blob-relative
+ * positions. PtrSrc is the blob itself; WinSrc reads positions below
+ * win_len from a local copy of the blob's head (an LDS row on the device, a
+ * heap buffer in the host test) and everything else from the blob. */
+struct PtrSrc {
+  const uint8_t *p;
+  WB_HD_OP uint8_t byte(uint32_t pos) const { return p[pos]; }
+  WB_HD_OP uint32_t u32(uint32_t pos) const { return fixed32_le(p + pos); }
+  WB_HD_OP uint64_t u64(uint32_t pos) const { return fixed64_le(p + pos); }
+};
+
+struct WinSrc {
+  const uint8_t *win; /* copy of rep[0, win_len); 4-B aligned on the device */
+  uint32_t win_len;
+  const uint8_t *rep;
+  WB_HD_OP uint8_t byte(uint32_t pos) const {
+    return pos < win_len ? win[pos] : rep[pos];
+  }
+  WB_HD_OP uint32_t u32(uint32_t pos) const {
+    if (pos + 4 > win_len) return fixed32_le(rep + pos);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if ((pos & 3u) == 0) return *(const uint32_t *)(win + pos);
+#endif
+    return (uint32_t)win[pos] | ((uint32_t)win[pos + 1] << 8) |
+           ((uint32_t)win[pos + 2] << 16) | ((uint32_t)win[pos + 3] << 24);
+  }
+  WB_HD_OP uint64_t u64(uint32_t pos) const {
+    if (pos + 8 > win_len) return fixed64_le(rep + pos);
+    return (uint64_t)u32(pos) | ((uint64_t)u32(pos + 4) << 32);
+  }
+};
+
+/* Window staging: the window of a blob of `len` bytes under a window size W
+ * (a multiple of 16) holds its first min(len, W) bytes, fetched as 16 B
+ * chunks from the blob's first byte. A chunk is fetched only if it starts
+ * before the end of the blob and of the window, so staging reads at most
+ * 15 B past the blob's end (inside every blob arena's 16 B over-allocation)
+ * and never below the blob's start. */
+WB_HD uint32_t win_bytes(uint32_t len, uint32_t W) { return len < W ? len : W; }
+WB_HD uint32_t win_chunks(uint32_t len, uint32_t W) {
+  return (win_bytes(len, W) + 15u) / 16u;
+}
+
+/* varint32 decode at src[pos..]; returns bytes consumed (1..5), 0 on
+ * error/overrun. At least `avail` bytes must be readable from pos. */
+template <class Src>
+WB_HD uint32_t varint32_src(const Src &src, uint32_t pos, uint32_t avail,
+                            uint32_t *out) {
   uint32_t result = 0;
 #pragma unroll
   for (uint32_t i = 0; i < 5; i++) {
     if (i >= avail) return 0;
-    uint32_t byte = p[i];
+    uint32_t byte = src.byte(pos + i);
     if (byte & 0x80) {
       result |= (byte & 0x7F) << (7 * i);
     } else {
@@ -79,6 +125,9 @@ WB_HD uint32_t varint32(const uint8_t *p, uint32_t avail, uint32_t *out) {
     }
   }
   return 0;
+}
+WB_HD uint32_t varint32(const uint8_t *p, uint32_t avail, uint32_t *out) {
+  return varint32_src(PtrSrc{p}, 0, avail, out);
 }
 
 /* 32-bit FNV-1a fingerprint of the STORED key bytes ([cf LE4 | key] for cf
@@ -153,32 +202,33 @@ struct WalkTotals {
   uint64_t hdr_seq;       /* header seq field */
 };
 
-/* Sequential walk over one rep blob, calling f(rec, index) for every
- * seq-consuming record in order. Corruption (truncated slice, bad varint,
- * unknown tag, count mismatch — write_batch.cc Iterate contract) => ok = 0
- * (f may have been called for a prefix; callers gate on ok). */
-template <class F>
-WB_HD WalkTotals walk_f(const uint8_t *rep, uint32_t len, F &&f) {
+/* Sequential walk over one rep blob read through `src`, calling
+ * f(rec, index) for every seq-consuming record in order. Corruption
+ * (truncated slice, bad varint, unknown tag, count mismatch — write_batch.cc
+ * Iterate contract) => ok = 0 (f may have been called for a prefix; callers
+ * gate on ok). The one parser: every byte source shares these decisions. */
+template <class Src, class F>
+WB_HD WalkTotals walk_src(const Src &src, uint32_t len, F &&f) {
   WalkTotals t = {0, 0, 0, 0, 0, 0, 0};
   if (len < kHeaderBytes) return t;
-  t.hdr_seq = fixed64_le(rep);
-  t.hdr_count = fixed32_le(rep + 8);
+  t.hdr_seq = src.u64(0);
+  t.hdr_count = src.u32(8);
   uint32_t pos = kHeaderBytes;
   uint32_t consumed = 0, nrec = 0, payload = 0, payload16 = 0;
   while (pos < len) {
-    uint8_t tag = rep[pos++];
+    uint8_t tag = src.byte(pos++);
     uint8_t bt = base_tag(tag);
     int ns = nslices(bt);
     if (ns < 0) return t; /* unknown tag */
     uint32_t cf = 0;
     if (has_cf_prefix(tag)) {
-      uint32_t c = varint32(rep + pos, len - pos, &cf);
+      uint32_t c = varint32_src(src, pos, len - pos, &cf);
       if (c == 0) return t;
       pos += c;
     }
     uint32_t off[2] = {0, 0}, slen[2] = {0, 0};
     for (int s = 0; s < ns; s++) {
-      uint32_t n, c = varint32(rep + pos, len - pos, &n);
+      uint32_t n, c = varint32_src(src, pos, len - pos, &n);
       if (c == 0) return t;
       pos += c;
       if (pos + n > len || n > len) return t;
@@ -215,6 +265,12 @@ WB_HD WalkTotals walk_f(const uint8_t *rep, uint32_t len, F &&f) {
   t.payload16 = payload16;
   t.ok = 1;
   return t;
+}
+
+/* The walk over the blob itself. */
+template <class F>
+WB_HD WalkTotals walk_f(const uint8_t *rep, uint32_t len, F &&f) {
+  return walk_src(PtrSrc{rep}, len, f);
 }
 
 struct NullEmit {
