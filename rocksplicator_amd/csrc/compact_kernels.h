@@ -48,21 +48,6 @@ __host__ __device__ inline uint32_t cp_align16(uint64_t n) {
   return (uint32_t)((n + 15) & ~15ULL);
 }
 
-/* inclusive scan of one ScSum per thread over a block of 256 */
-__device__ inline ScSum cp_block_scan(ScSum v, ScSum *sh) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int ofs = 1; ofs < 256; ofs <<= 1) {
-    ScSum a = sh[threadIdx.x];
-    ScSum b = threadIdx.x >= (uint32_t)ofs ? sh[threadIdx.x - ofs]
-                                           : ScSum{0, 0, 0};
-    __syncthreads();
-    sh[threadIdx.x] = sc_add(a, b);
-    __syncthreads();
-  }
-  return sh[threadIdx.x];
-}
-
 /* One thread per sorted candidate; the liveness rules are k_sc_resolve's. A
  * live Merge head must have been folded (k_sc_fold leaves it unfolded only
  * when its value would not fit 32 bits). */
@@ -92,6 +77,8 @@ __global__ void __launch_bounds__(256) k_cp_resolve(
           bytes = 0xFFFF0000ull;
       }
     } else if (head && c.type == wb::kValue) {
+      /* sc_tomb_kills, written out: through the helper this kernel compiles
+       * to two more SGPRs (profiles/readpath) */
       const uint8_t *key = store + c.koff;
       live = true;
       for (uint32_t t = 0; t < ntomb && live; t++) {
@@ -113,7 +100,7 @@ __global__ void __launch_bounds__(256) k_cp_resolve(
       }
     }
   }
-  ScSum inc = cp_block_scan(v, sh);
+  ScSum inc = sc_block_scan(v, sh);
   if (i < n)
     items[i] = {inc.bytes - v.bytes, (inc.cnt - v.cnt) | (v.cnt << 31),
                 (uint32_t)v.bytes};
@@ -135,7 +122,7 @@ __global__ void __launch_bounds__(256) k_cp_finish(
   for (uint32_t base = 0; base < nblocks; base += 256) {
     uint32_t i = base + threadIdx.x;
     ScSum v = i < nblocks ? bsums[i] : ScSum{0, 0, 0};
-    ScSum inc = sc_add(cp_block_scan(v, sh), carry);
+    ScSum inc = sc_add(sc_block_scan(v, sh), carry);
     if (i < nblocks) bsums[i] = {inc.bytes - v.bytes, inc.cnt - v.cnt, 0};
     __syncthreads();
     if (threadIdx.x == 255) carry = inc;

@@ -22,6 +22,10 @@
  * are shard-grouped per tick and record headers are emitted in stream order
  * (seq accounting per rocksdb_assumption_test.cpp:136-187).
  *
+ * The device read paths keep their kernels in headers included below inside
+ * namespace gra (mg_kernels.h, scan_kernels.h, compact_kernels.h) and their
+ * host drivers here; their staging buffers are dev_buf.h's owning types.
+ *
  * No CPU fallback exists for this path: engine creation fails loudly
  * without a HIP device.
  */
@@ -43,6 +47,7 @@
 #include <vector>
 
 #include "../../include/rocksplicator_gpu.h"
+#include "dev_buf.h"
 #include "fold.h"
 #include "host_store.h"
 #include "part_copy.h"
@@ -458,446 +463,8 @@ __global__ void k_rundesc(const GroupDesc *__restrict__ groups, uint32_t ngroups
   out[g] = rd;
 }
 
-/* ---------------- device read serving (multiget) ----------------
- * One block per query: scan the shard's runs newest->oldest; per matching
- * entry track the max-seq terminator (Put/Delete/SingleDelete), whether any
- * Merge sits above it (=> host fold), and the max covering range-tombstone
- * seq. Followers serve reads in rocksplicator deployments; with the
- * memtable resident in HBM the lookup runs there too. */
-struct RunView {
-  uint64_t hdr_off, payload_off;
-  uint32_t n_entries, pay_rel_base;
-};
-
-__device__ inline int dev_memcmp(const uint8_t *a, const uint8_t *b, uint32_t n) {
-  for (uint32_t i = 0; i < n; i++) {
-    if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
-  }
-  return 0;
-}
-
-/* per-query raw seq info so mixed device/host shards can merge the device
- * verdict with a host-run probe (gra_multiget) */
-struct MgExtra {
-  uint64_t term_seq, merge_seq, rd_seq;
-  uint32_t term_type, _pad;
-};
-
-__global__ void k_multiget(const uint8_t *__restrict__ store,
-                           const RunView *__restrict__ runs, uint32_t nruns,
-                           const GraKeyRef *__restrict__ keys,
-                           const uint8_t *__restrict__ keybuf, uint32_t nq,
-                           uint8_t *__restrict__ valbuf, uint32_t val_stride,
-                           GraGetResult *__restrict__ out,
-                           MgExtra *__restrict__ extra, int fold_u64) {
-  __shared__ uint64_t sh_term_seq[256];
-  __shared__ uint64_t sh_term_ref[256]; /* (run<<32)|entry, ~0 = none */
-  __shared__ uint64_t sh_merge_seq[256];
-  __shared__ uint64_t sh_rd_seq[256];
-  uint32_t q = blockIdx.x;
-  if (q >= nq) return;
-  const uint8_t *key = keybuf + keys[q].off;
-  uint32_t klen = keys[q].len;
-  uint32_t qpref = wb::key_fnv_fold(wb::kFnvBasis32, key, klen);
-  uint64_t term_seq = 0, term_ref = ~0ULL, merge_seq = 0, rd_seq = 0;
-  for (uint32_t r = 0; r < nruns; r++) {
-    RunView rv = runs[r];
-    const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv.hdr_off);
-    const uint8_t *pay = store + rv.payload_off;
-    for (uint32_t i = threadIdx.x; i < rv.n_entries; i += blockDim.x) {
-      wb::RecHdr h = hdrs[i];
-      if (h.type != wb::kRangeDeletion &&
-          (h.key_len != klen || h.kpref != qpref))
-        continue; /* header-only reject: no payload touch */
-      uint32_t rel = h.kv_off - rv.pay_rel_base;
-      if (h.type == wb::kRangeDeletion) {
-        const uint8_t *b = pay + rel, *e2 = pay + rel + h.key_len;
-        uint32_t bl = h.key_len, el = h.val_len;
-        int c1 = dev_memcmp(b, key, bl < klen ? bl : klen);
-        if (c1 > 0 || (c1 == 0 && bl > klen)) continue;
-        int c2 = dev_memcmp(key, e2, klen < el ? klen : el);
-        if (c2 > 0 || (c2 == 0 && klen >= el)) continue;
-        if (h.seq > rd_seq) rd_seq = h.seq;
-        continue;
-      }
-      if (dev_memcmp(pay + rel, key, klen) != 0) /* len+prefix pre-checked */
-        continue;
-      if (h.type == wb::kMerge) {
-        if (h.seq > merge_seq) merge_seq = h.seq;
-      } else if (h.seq > term_seq) {
-        term_seq = h.seq;
-        term_ref = ((uint64_t)r << 32) | i;
-      }
-    }
-  }
-  uint32_t tid = threadIdx.x;
-  sh_term_seq[tid] = term_seq;
-  sh_term_ref[tid] = term_ref;
-  sh_merge_seq[tid] = merge_seq;
-  sh_rd_seq[tid] = rd_seq;
-  __syncthreads();
-  for (uint32_t ofs = blockDim.x / 2; ofs > 0; ofs >>= 1) {
-    if (tid < ofs) {
-      if (sh_term_seq[tid + ofs] > sh_term_seq[tid]) {
-        sh_term_seq[tid] = sh_term_seq[tid + ofs];
-        sh_term_ref[tid] = sh_term_ref[tid + ofs];
-      }
-      if (sh_merge_seq[tid + ofs] > sh_merge_seq[tid])
-        sh_merge_seq[tid] = sh_merge_seq[tid + ofs];
-      if (sh_rd_seq[tid + ofs] > sh_rd_seq[tid])
-        sh_rd_seq[tid] = sh_rd_seq[tid + ofs];
-    }
-    __syncthreads();
-  }
-  uint64_t T = sh_term_seq[0], M = sh_merge_seq[0], RD = sh_rd_seq[0];
-  uint64_t ref = sh_term_ref[0];
-  uint8_t term_type = 0xFF;
-  wb::RecHdr h = {};
-  RunView rv = {};
-  if (ref != ~0ULL) {
-    rv = runs[ref >> 32];
-    h = ((const wb::RecHdr *)(store + rv.hdr_off))[(uint32_t)ref];
-    term_type = h.type;
-  }
-  if (tid == 0 && extra) { /* raw verdict for host-side merging */
-    extra[q].term_seq = T;
-    extra[q].merge_seq = M;
-    extra[q].rd_seq = RD;
-    extra[q].term_type = term_type;
-  }
-  uint64_t floor_seq = T > RD ? T : RD;
-  if (M > floor_seq && fold_u64) {
-    /* fold_on_device, u64add: a second pass over the runs sums the operands
-     * above the floor (integer adds commute: any order). Long chains land
-     * here — they overflow the hash join's candidate cap. */
-    uint64_t acc = 0;
-    for (uint32_t r = 0; r < nruns; r++) {
-      RunView rv2 = runs[r];
-      const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv2.hdr_off);
-      const uint8_t *pay = store + rv2.payload_off;
-      for (uint32_t i = tid; i < rv2.n_entries; i += blockDim.x) {
-        wb::RecHdr h2 = hdrs[i];
-        if (h2.type != wb::kMerge || h2.seq <= floor_seq ||
-            h2.key_len != klen || h2.kpref != qpref)
-          continue;
-        const uint8_t *k2 = pay + (h2.kv_off - rv2.pay_rel_base);
-        if (dev_memcmp(k2, key, klen) != 0) continue;
-        acc = fold::add_wrap(acc, fold::load_u64le(k2 + klen, h2.val_len));
-      }
-    }
-    __syncthreads(); /* the shared arrays were read above */
-    sh_term_seq[tid] = acc;
-    __syncthreads();
-    for (uint32_t ofs = blockDim.x / 2; ofs > 0; ofs >>= 1) {
-      if (tid < ofs)
-        sh_term_seq[tid] =
-            fold::add_wrap(sh_term_seq[tid], sh_term_seq[tid + ofs]);
-      __syncthreads();
-    }
-    if (tid == 0) {
-      uint64_t v = sh_term_seq[0];
-      if (T > RD && term_type == wb::kValue) /* base: the Put above RD */
-        v = fold::add_wrap(
-            v, fold::load_u64le(store + rv.payload_off +
-                                    (h.kv_off - rv.pay_rel_base) + h.key_len,
-                                h.val_len));
-      fold::store_u64le(valbuf + (size_t)q * val_stride, v, val_stride);
-      out[q].status = GRA_GET_FOUND;
-      out[q].vlen = 8; /* true length (caller sees truncation) */
-    }
-    return;
-  }
-  if (M > floor_seq) { /* live merge operands: fold on the host */
-    if (tid == 0) {
-      out[q].status = GRA_GET_NEEDS_HOST;
-      out[q].vlen = 0;
-    }
-    return;
-  }
-  if (T == 0 || T <= RD || ref == ~0ULL) {
-    if (tid == 0) {
-      out[q].status = GRA_GET_MISS;
-      out[q].vlen = 0;
-    }
-    return;
-  }
-  if (h.type != wb::kValue) { /* Delete/SingleDelete terminator */
-    if (tid == 0) {
-      out[q].status = GRA_GET_MISS;
-      out[q].vlen = 0;
-    }
-    return;
-  }
-  uint32_t vlen = h.val_len < val_stride ? h.val_len : val_stride;
-  const uint8_t *src = store + rv.payload_off + (h.kv_off - rv.pay_rel_base) +
-                       h.key_len;
-  uint8_t *dst = valbuf + (size_t)q * val_stride;
-  for (uint32_t b = tid; b < vlen; b += blockDim.x) dst[b] = src[b];
-  if (tid == 0) {
-    out[q].status = GRA_GET_FOUND;
-    out[q].vlen = h.val_len; /* true length (caller sees truncation) */
-  }
-}
-
-/* Lazy read-index build: one coalesced pass over a run fills every
- * header's key fingerprint from the STORED key bytes (contiguous in the
- * payload). Launched at a run's first multiget — apply-time fills all
- * measured 160-480 us/tick against the headline (see k_emit). */
-__global__ void k_kpref(uint8_t *__restrict__ store,
-                        const RunView *__restrict__ runs) {
-  RunView rv = runs[blockIdx.y];
-  wb::RecHdr *hdrs = (wb::RecHdr *)(store + rv.hdr_off);
-  const uint8_t *pay = store + rv.payload_off;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rv.n_entries;
-       i += gridDim.x * blockDim.x) {
-    wb::RecHdr h = hdrs[i];
-    hdrs[i].kpref =
-        (h.type == wb::kRangeDeletion)
-            ? 0 /* tombstones are range-matched, not hash-matched */
-            : wb::key_fnv_fold(wb::kFnvBasis32,
-                               pay + (h.kv_off - rv.pay_rel_base), h.key_len);
-  }
-}
-
-/* ---------------- hash-join multiget ----------------
- * The linear per-query scan is header-bandwidth bound (nq × entries × 24 B).
- * Invert it: ONE coalesced pass over all entries probes an open-addressed
- * query-fingerprint table (kpref -> query idx) and appends the rare
- * matches to a candidate list; tiny resolve kernels then pick per-query
- * winners by seq. Traffic: O(entries + matches) instead of O(nq × entries).
- * Range tombstones are collected in the same pass and tested per query
- * separately (they cover key RANGES — not hash-matchable). Overflow of
- * either list falls back to the per-query scan kernel. */
-struct MgCand {
-  uint32_t qidx, run, entry, type;
-  uint64_t seq;
-};
-struct MgTomb {
-  uint32_t run, entry, _pad0, _pad1;
-  uint64_t seq;
-};
-
-__global__ void k_mg_scan(const uint8_t *__restrict__ store,
-                          const RunView *__restrict__ runs,
-                          const uint64_t *__restrict__ qtab, uint32_t qmask,
-                          const GraKeyRef *__restrict__ keys,
-                          const uint8_t *__restrict__ keybuf,
-                          MgCand *__restrict__ cands,
-                          uint32_t *__restrict__ ncand, uint32_t cand_cap,
-                          MgTomb *__restrict__ tombs,
-                          uint32_t *__restrict__ ntomb, uint32_t tomb_cap) {
-  uint32_t r = blockIdx.y;
-  RunView rv = runs[r];
-  const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv.hdr_off);
-  const uint8_t *pay = store + rv.payload_off;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rv.n_entries;
-       i += gridDim.x * blockDim.x) {
-    wb::RecHdr h = hdrs[i];
-    if (h.type == wb::kRangeDeletion) {
-      uint32_t slot = atomicAdd(ntomb, 1u);
-      if (slot < tomb_cap) tombs[slot] = {r, i, 0, 0, h.seq};
-      continue;
-    }
-    uint32_t s = h.kpref & qmask;
-    while (true) { /* linear probe; duplicates of a fingerprint chain on */
-      uint64_t e = qtab[s];
-      if (e == 0) break;
-      if ((uint32_t)(e >> 32) == h.kpref) {
-        uint32_t qidx = (uint32_t)e - 1;
-        uint32_t klen = keys[qidx].len;
-        if (h.key_len == klen &&
-            dev_memcmp(pay + (h.kv_off - rv.pay_rel_base),
-                       keybuf + keys[qidx].off, klen) == 0) {
-          uint32_t slot = atomicAdd(ncand, 1u);
-          if (slot < cand_cap) cands[slot] = {qidx, r, i, h.type, h.seq};
-        }
-      }
-      s = (s + 1) & qmask;
-    }
-  }
-}
-
-__global__ void k_mg_resolve1(const MgCand *__restrict__ cands,
-                              const uint32_t *__restrict__ ncand_p,
-                              uint32_t cap,
-                              unsigned long long *__restrict__ term_pack,
-                              unsigned long long *__restrict__ merge_seq) {
-  uint32_t n = *ncand_p < cap ? *ncand_p : cap; /* device-side bound: no
-                                                   host sync between scan
-                                                   and resolve */
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  MgCand c = cands[i];
-  if (c.type == wb::kMerge)
-    atomicMax(&merge_seq[c.qidx], (unsigned long long)c.seq);
-  else /* seqs are unique per shard: the packed max has ONE winner */
-    atomicMax(&term_pack[c.qidx],
-              (unsigned long long)((c.seq << 8) | c.type));
-}
-
-__global__ void k_mg_tombs(const uint8_t *__restrict__ store,
-                           const RunView *__restrict__ runs,
-                           const MgTomb *__restrict__ tombs,
-                           const uint32_t *__restrict__ ntomb_p, uint32_t cap,
-                           const GraKeyRef *__restrict__ keys,
-                           const uint8_t *__restrict__ keybuf, uint32_t nq,
-                           unsigned long long *__restrict__ rd_seq) {
-  uint32_t ntomb = *ntomb_p < cap ? *ntomb_p : cap;
-  uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  const uint8_t *key = keybuf + keys[q].off;
-  uint32_t klen = keys[q].len;
-  uint64_t best = 0;
-  for (uint32_t t = 0; t < ntomb; t++) {
-    MgTomb mt = tombs[t];
-    RunView rv = runs[mt.run];
-    const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv.hdr_off);
-    wb::RecHdr h = hdrs[mt.entry];
-    const uint8_t *pay = store + rv.payload_off;
-    uint32_t rel = h.kv_off - rv.pay_rel_base;
-    const uint8_t *b = pay + rel, *e2 = pay + rel + h.key_len;
-    uint32_t bl = h.key_len, el = h.val_len;
-    int c1 = dev_memcmp(b, key, bl < klen ? bl : klen);
-    if (c1 > 0 || (c1 == 0 && bl > klen)) continue;
-    int c2 = dev_memcmp(key, e2, klen < el ? klen : el);
-    if (c2 > 0 || (c2 == 0 && klen >= el)) continue;
-    if (h.seq > best) best = h.seq;
-  }
-  rd_seq[q] = best;
-}
-
-__global__ void k_mg_resolve2(const MgCand *__restrict__ cands,
-                              const uint32_t *__restrict__ ncand_p,
-                              uint32_t cap,
-                              const unsigned long long *__restrict__ term_pack,
-                              unsigned long long *__restrict__ winner_ref) {
-  uint32_t n = *ncand_p < cap ? *ncand_p : cap;
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  MgCand c = cands[i];
-  if (c.type != wb::kMerge &&
-      term_pack[c.qidx] == (unsigned long long)((c.seq << 8) | c.type))
-    winner_ref[c.qidx] = ((unsigned long long)c.run << 32) | c.entry;
-}
-
-/* fold_on_device, u64add: every Merge candidate above its query's floor
- * max(T, RD) adds its operand into acc[qidx]. Hot counters put most of a
- * wave on one query, so lanes that share a qidx are summed in the wave
- * first and their leader issues the one global atomic; a lane alone on its
- * query adds directly. Integer adds commute: arrival order is immaterial. */
-__global__ void __launch_bounds__(256) k_mg_fold(
-    const uint8_t *__restrict__ store, const RunView *__restrict__ runs,
-    const MgCand *__restrict__ cands, const uint32_t *__restrict__ ncand_p,
-    uint32_t cap, const unsigned long long *__restrict__ term_pack,
-    const unsigned long long *__restrict__ rd_seq,
-    unsigned long long *__restrict__ acc) {
-  uint32_t n = *ncand_p < cap ? *ncand_p : cap;
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t lane = threadIdx.x & 63;
-  bool active = false;
-  uint32_t q = 0;
-  uint64_t v = 0;
-  if (i < n) {
-    MgCand c = cands[i];
-    if (c.type == wb::kMerge) {
-      uint64_t T = term_pack[c.qidx] >> 8, RD = rd_seq[c.qidx];
-      if (c.seq > (T > RD ? T : RD)) {
-        RunView rv = runs[c.run];
-        wb::RecHdr h = ((const wb::RecHdr *)(store + rv.hdr_off))[c.entry];
-        v = fold::load_u64le(store + rv.payload_off +
-                                 (h.kv_off - rv.pay_rel_base) + h.key_len,
-                             h.val_len);
-        q = c.qidx;
-        active = true;
-      }
-    }
-  }
-  /* wave-uniform loop: peel one query per turn */
-  for (unsigned long long m = __ballot(active); m; m = __ballot(active)) {
-    uint32_t leader = (uint32_t)__ffsll((long long)m) - 1;
-    uint32_t lq = __shfl(q, leader, 64);
-    bool mine = active && q == lq;
-    unsigned long long grp = __ballot(mine);
-    uint64_t sum = v;
-    if (grp & (grp - 1)) { /* more than one lane: wave-reduce the group */
-      sum = mine ? v : 0;
-      for (int ofs = 32; ofs > 0; ofs >>= 1)
-        sum = fold::add_wrap(
-            sum, (uint64_t)__shfl_xor((unsigned long long)sum, ofs, 64));
-    }
-    if (lane == leader) atomicAdd(&acc[lq], (unsigned long long)sum);
-    if (mine) active = false;
-  }
-}
-
-__global__ void k_mg_emit(const uint8_t *__restrict__ store,
-                          const RunView *__restrict__ runs,
-                          const unsigned long long *__restrict__ term_pack,
-                          const unsigned long long *__restrict__ merge_seq,
-                          const unsigned long long *__restrict__ rd_seq,
-                          const unsigned long long *__restrict__ winner_ref,
-                          uint32_t nq, uint8_t *__restrict__ valbuf,
-                          uint32_t val_stride, GraGetResult *__restrict__ out,
-                          MgExtra *__restrict__ extra,
-                          const unsigned long long *__restrict__ acc) {
-  uint32_t q = blockIdx.x;
-  if (q >= nq) return;
-  uint64_t tp = term_pack[q];
-  uint64_t T = tp >> 8, M = merge_seq[q], RD = rd_seq[q];
-  uint8_t ttype = tp ? (uint8_t)tp : 0xFF;
-  if (threadIdx.x == 0 && extra) {
-    extra[q].term_seq = T;
-    extra[q].merge_seq = M;
-    extra[q].rd_seq = RD;
-    extra[q].term_type = ttype;
-  }
-  uint64_t fl = T > RD ? T : RD;
-  if (M > fl && acc) { /* fold_on_device, u64add: base + k_mg_fold's sum */
-    if (threadIdx.x == 0) {
-      uint64_t v = acc[q];
-      if (T > RD && ttype == wb::kValue) {
-        unsigned long long ref = winner_ref[q];
-        RunView rv = runs[ref >> 32];
-        wb::RecHdr h = ((const wb::RecHdr *)(store + rv.hdr_off))[(uint32_t)ref];
-        v = fold::add_wrap(
-            v, fold::load_u64le(store + rv.payload_off +
-                                    (h.kv_off - rv.pay_rel_base) + h.key_len,
-                                h.val_len));
-      }
-      fold::store_u64le(valbuf + (size_t)q * val_stride, v, val_stride);
-      out[q].status = GRA_GET_FOUND;
-      out[q].vlen = 8; /* true length (caller sees truncation) */
-    }
-    return;
-  }
-  if (M > fl) {
-    if (threadIdx.x == 0) {
-      out[q].status = GRA_GET_NEEDS_HOST;
-      out[q].vlen = 0;
-    }
-    return;
-  }
-  if (T == 0 || T <= RD || ttype != wb::kValue) {
-    if (threadIdx.x == 0) {
-      out[q].status = GRA_GET_MISS;
-      out[q].vlen = 0;
-    }
-    return;
-  }
-  unsigned long long ref = winner_ref[q];
-  RunView rv = runs[ref >> 32];
-  const wb::RecHdr *hdrs = (const wb::RecHdr *)(store + rv.hdr_off);
-  wb::RecHdr h = hdrs[(uint32_t)ref];
-  uint32_t vlen = h.val_len < val_stride ? h.val_len : val_stride;
-  const uint8_t *src =
-      store + rv.payload_off + (h.kv_off - rv.pay_rel_base) + h.key_len;
-  uint8_t *dst = valbuf + (size_t)q * val_stride;
-  for (uint32_t b = threadIdx.x; b < vlen; b += blockDim.x) dst[b] = src[b];
-  if (threadIdx.x == 0) {
-    out[q].status = GRA_GET_FOUND;
-    out[q].vlen = h.val_len;
-  }
-}
+/* ---------------- device read serving (gra_multiget) ---------------- */
+#include "mg_kernels.h"
 
 /* ---------------- device range scan (gra_scan) ---------------- */
 #include "scan_kernels.h"
@@ -1135,41 +702,37 @@ struct GraEngine {
   Slot slots[kSlots];
   std::deque<TickRec> pending;
   std::vector<hipEvent_t> event_pool;
+  /* The two staging caches own only device and pinned memory (dev_buf.h), so
+   * they may be destroyed at any position among the members. */
   /* multiget staging cache (grow-only; guarded by mu) */
+  struct MgCounts {
+    uint32_t ncand, ntomb;
+  };
   struct MgCache {
-    RunView *d_runs = nullptr;
-    GraKeyRef *d_keys = nullptr;
-    uint8_t *d_keybuf = nullptr, *d_valbuf = nullptr;
-    GraGetResult *d_out = nullptr;
-    void *d_extra = nullptr; /* MgExtra[] for mixed-shard merging */
-    void *d_qtab = nullptr;  /* hash-join: query fingerprint table (u64) */
-    void *d_cands = nullptr; /* MgCand[] matches */
-    void *d_tombs = nullptr; /* MgTomb[] range tombstones seen in the scan */
-    void *d_aux = nullptr;   /* 5 x nq u64: term_pack/merge/rd/winner/acc */
-    uint32_t *d_counts = nullptr; /* {ncand, ntomb} */
-    uint32_t *h_counts = nullptr; /* pinned mirror */
-    size_t runs_cap = 0, keys_cap = 0, keybuf_cap = 0, valbuf_cap = 0,
-           out_cap = 0, extra_cap = 0, qtab_cap = 0, cands_cap = 0,
-           tombs_cap = 0, aux_cap = 0;
+    DevBuf<RunView> d_runs;
+    DevBuf<GraKeyRef> d_keys;
+    DevBuf<uint8_t> d_keybuf, d_valbuf;
+    DevBuf<GraGetResult> d_out;
+    DevBuf<MgExtra> d_extra;  /* for mixed-shard merging */
+    DevBuf<uint64_t> d_qtab;  /* hash-join: query fingerprint table */
+    DevBuf<MgCand> d_cands;   /* matches */
+    DevBuf<MgTomb> d_tombs;   /* range tombstones seen in the scan */
+    DevBuf<unsigned long long> d_aux; /* 5 x nq: term_pack/merge/rd/winner/acc */
+    DevMirror<MgCounts> counts;
   } mg;
   /* range-scan staging cache (grow-only; guarded by mu) */
   struct ScCache {
-    RunView *d_runs = nullptr;
-    uint8_t *d_bounds = nullptr, *d_out = nullptr;
-    ScCand *d_cands = nullptr;
-    ScTomb *d_tombs = nullptr;
-    ScItem *d_items = nullptr;
-    ScHead *d_heads = nullptr; /* fold_on_device: live Merge heads */
-    ScFold *d_folds = nullptr; /* fold_on_device: per-candidate fold verdict */
-    ScSum *d_bsums = nullptr;
-    GraScanEntry *d_ents = nullptr;
-    ScCtl *d_ctl = nullptr;
-    ScCtl *h_ctl = nullptr; /* pinned mirror */
-    CpCtl *d_cp = nullptr;  /* gra_compact's result block */
-    CpCtl *h_cp = nullptr;  /* pinned mirror */
-    size_t runs_cap = 0, bounds_cap = 0, out_cap = 0, cands_cap = 0,
-           tombs_cap = 0, items_cap = 0, bsums_cap = 0, ents_cap = 0,
-           heads_cap = 0, folds_cap = 0;
+    DevBuf<RunView> d_runs;
+    DevBuf<uint8_t> d_bounds, d_out;
+    DevBuf<ScCand> d_cands;
+    DevBuf<ScTomb> d_tombs;
+    DevBuf<ScItem> d_items;
+    DevBuf<ScHead> d_heads; /* fold_on_device: live Merge heads */
+    DevBuf<ScFold> d_folds; /* fold_on_device: per-candidate fold verdict */
+    DevBuf<ScSum> d_bsums;
+    DevBuf<GraScanEntry> d_ents;
+    DevMirror<ScCtl> ctl;
+    DevMirror<CpCtl> cp;   /* gra_compact's result block */
     uint32_t cand_cap = 0; /* candidate records the sort buffers hold */
   } sc;
   /* drain-host pinned arena pool. DECLARED BEFORE shards: runs hold
@@ -1416,19 +979,6 @@ GraEngine::~GraEngine() {
     if (s.h_err) (void)hipHostFree(s.h_err);
     if (s.h_descs) (void)hipHostFree(s.h_descs);
   }
-  for (void *p : {(void *)mg.d_runs, (void *)mg.d_keys, (void *)mg.d_keybuf,
-                  (void *)mg.d_valbuf, (void *)mg.d_out, mg.d_extra,
-                  mg.d_qtab, mg.d_cands, mg.d_tombs, mg.d_aux,
-                  (void *)mg.d_counts})
-    if (p) (void)hipFree(p);
-  if (mg.h_counts) (void)hipHostFree(mg.h_counts);
-  for (void *p : {(void *)sc.d_runs, (void *)sc.d_bounds, (void *)sc.d_out,
-                  (void *)sc.d_cands, (void *)sc.d_tombs, (void *)sc.d_items,
-                  (void *)sc.d_bsums, (void *)sc.d_ents, (void *)sc.d_ctl,
-                  (void *)sc.d_heads, (void *)sc.d_folds, (void *)sc.d_cp})
-    if (p) (void)hipFree(p);
-  if (sc.h_ctl) (void)hipHostFree(sc.h_ctl);
-  if (sc.h_cp) (void)hipHostFree(sc.h_cp);
   for (int i = 0; i < 2; i++) {
     if (d_stage_blobs_bufs[i]) (void)hipFree(d_stage_blobs_bufs[i]);
     if (d_stage_descs_bufs[i]) (void)hipFree(d_stage_descs_bufs[i]);
@@ -2347,6 +1897,21 @@ int gra_get(GraDb *db, const void *key, size_t klen, void *buf, size_t cap,
   return GRA_OK;
 }
 
+static RunView view_of(const Run &r) {
+  return {r.hdr_cur, r.payload_cur, r.n_entries, r.pay_rel_base};
+}
+
+/* grid.x of the one-row-per-run kernels: 256-thread blocks for the longest
+ * run, clamped to [1, clamp] (the kernels stride past the clamp) */
+static uint32_t longest_run_blocks(const std::vector<RunView> &views,
+                                   uint32_t clamp) {
+  uint64_t max_run = 0;
+  for (const auto &v : views)
+    max_run = v.n_entries > max_run ? v.n_entries : max_run;
+  uint64_t bx = (max_run + 255) / 256;
+  return bx > clamp ? clamp : bx == 0 ? 1u : (uint32_t)bx;
+}
+
 int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
                  const uint8_t *keybuf, size_t keybuf_len, uint8_t *valbuf,
                  uint32_t val_stride, GraGetResult *out) {
@@ -2369,7 +1934,7 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
         host_runs.push_back(*it); /* oldest..newest order irrelevant: probe
                                      tracks max seqs */
       } else {
-        views.push_back({r.hdr_cur, r.payload_cur, r.n_entries, r.pay_rel_base});
+        views.push_back(view_of(r));
         if (!r.kpref_built) unbuilt.push_back(*it); /* racy pre-filter:
                                      re-checked under e->mu (rebuilds are
                                      idempotent anyway) */
@@ -2390,30 +1955,8 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
   /* grow-only device staging cached on the engine (serialized with other
    * engine ops by mu; a serving deployment would shard this per stream) */
   std::lock_guard<std::mutex> lk_engine(e->mu);
-  auto grow = [](auto **p, size_t *cap, size_t need) {
-    if (*cap >= need) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    size_t want = need + need / 2 + 64;
-    if (hipMalloc(p, want) != hipSuccess) return false;
-    *cap = want;
-    return true;
-  };
   size_t vb = (size_t)nq * val_stride;
   auto &mg = e->mg;
-  if (!grow(&mg.d_runs, &mg.runs_cap, views.size() * sizeof(RunView)) ||
-      !grow(&mg.d_keys, &mg.keys_cap, nq * sizeof(GraKeyRef)) ||
-      !grow(&mg.d_keybuf, &mg.keybuf_cap, keybuf_len + 16) ||
-      !grow(&mg.d_valbuf, &mg.valbuf_cap, vb + 16) ||
-      !grow(&mg.d_out, &mg.out_cap, nq * sizeof(GraGetResult))) {
-    g_err = "gra_multiget: allocation failed";
-    return GRA_ERR;
-  }
-  RunView *d_runs = mg.d_runs;
-  GraKeyRef *d_keys = mg.d_keys;
-  uint8_t *d_keybuf = mg.d_keybuf, *d_valbuf = mg.d_valbuf;
-  GraGetResult *d_out = mg.d_out;
   const bool mixed = !host_runs.empty();
   /* The device fold answers FOUND only when it has seen every entry of the
    * key: a mixed call switches it off, since host runs may hold newer ones
@@ -2427,61 +1970,49 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
   while (qtab_size < 2 * nq) qtab_size <<= 1;
   uint32_t cand_cap = 4 * nq + 1024, tomb_cap = 4096;
   bool hashjoin = views.size() <= 65535;
-  if ((mixed && !grow(&mg.d_extra, &mg.extra_cap, nq * sizeof(MgExtra))) ||
+  /* with headroom: query batches of slowly growing size do not reallocate
+   * at every call */
+  if (!mg.d_runs.reserve_bytes(views.size() * sizeof(RunView), true) ||
+      !mg.d_keys.reserve_bytes(nq * sizeof(GraKeyRef), true) ||
+      !mg.d_keybuf.reserve_bytes(keybuf_len + 16, true) ||
+      !mg.d_valbuf.reserve_bytes(vb + 16, true) ||
+      !mg.d_out.reserve_bytes(nq * sizeof(GraGetResult), true) ||
+      (mixed && !mg.d_extra.reserve_bytes(nq * sizeof(MgExtra), true)) ||
       (hashjoin &&
-       (!grow(&mg.d_qtab, &mg.qtab_cap, qtab_size * 8) ||
-        !grow(&mg.d_cands, &mg.cands_cap, (size_t)cand_cap * sizeof(MgCand)) ||
-        !grow(&mg.d_tombs, &mg.tombs_cap, (size_t)tomb_cap * sizeof(MgTomb)) ||
-        !grow(&mg.d_aux, &mg.aux_cap, (size_t)nq * 8 * 5)))) {
+       (!mg.d_qtab.reserve_bytes(qtab_size * 8, true) ||
+        !mg.d_cands.reserve_bytes((size_t)cand_cap * sizeof(MgCand), true) ||
+        !mg.d_tombs.reserve_bytes((size_t)tomb_cap * sizeof(MgTomb), true) ||
+        !mg.d_aux.reserve_bytes((size_t)nq * 8 * 5, true))) ||
+      !mg.counts.ensure()) {
     g_err = "gra_multiget: allocation failed";
     return GRA_ERR;
   }
-  if (!mg.d_counts) {
-    if (hipMalloc(&mg.d_counts, 8) != hipSuccess) {
-      g_err = "gra_multiget: allocation failed";
-      return GRA_ERR;
-    }
-    if (hipHostMalloc(&mg.h_counts, 8) != hipSuccess) {
-      (void)hipFree(mg.d_counts);
-      mg.d_counts = nullptr;
-      g_err = "gra_multiget: allocation failed";
-      return GRA_ERR;
-    }
-  }
+  uint32_t *d_ncand = &mg.counts.d->ncand, *d_ntomb = &mg.counts.d->ntomb;
   /* lazy read-index build for first-served runs (single pass per run,
    * ordered before this call's lookup kernels on the same stream;
    * concurrent calls serialize on e->mu and re-check the flag) */
   std::vector<RunView> bviews;
   for (auto &rp : unbuilt) {
     if (!rp->kpref_built) {
-      bviews.push_back(
-          {rp->hdr_cur, rp->payload_cur, rp->n_entries, rp->pay_rel_base});
+      bviews.push_back(view_of(*rp));
       rp->kpref_built = true;
     }
   }
-  if (!bviews.empty()) {
-    size_t need = (views.size() > bviews.size() ? views.size()
-                                                : bviews.size()) *
-                  sizeof(RunView);
-    if (!grow(&mg.d_runs, &mg.runs_cap, need) ||
-        hipMemcpyAsync(mg.d_runs, bviews.data(),
+  if (!bviews.empty()) { /* a subset of views, which d_runs is sized for */
+    if (hipMemcpyAsync(mg.d_runs, bviews.data(),
                        bviews.size() * sizeof(RunView),
                        hipMemcpyHostToDevice, e->stream) != hipSuccess) {
       g_err = "gra_multiget: index build failed";
       return GRA_ERR;
     }
-    uint64_t maxe = 0;
-    for (auto &v : bviews)
-      maxe = v.n_entries > maxe ? v.n_entries : maxe;
-    uint32_t bx = (uint32_t)((maxe + 255) / 256);
-    if (bx > 256) bx = 256;
-    hipLaunchKernelGGL(k_kpref, dim3(bx, (uint32_t)bviews.size()), dim3(256),
-                       0, e->stream, e->d_store, mg.d_runs);
+    hipLaunchKernelGGL(k_kpref,
+                       dim3(longest_run_blocks(bviews, 256),
+                            (uint32_t)bviews.size()),
+                       dim3(256), 0, e->stream, e->d_store, mg.d_runs);
     if (hipGetLastError() != hipSuccess) {
       g_err = "gra_multiget: index build launch failed";
       return GRA_ERR;
     }
-    d_runs = mg.d_runs; /* grow may have reallocated */
   }
   std::vector<uint64_t> qtab;
   if (hashjoin) { /* host-built open-addressed fingerprint table */
@@ -2502,74 +2033,65 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
      * scan kernel. */
     bool use_hj = hashjoin && attempt == 0;
     do {
-      if (hipMemcpyAsync(d_runs, views.data(),
+      if (hipMemcpyAsync(mg.d_runs, views.data(),
                          views.size() * sizeof(RunView),
                          hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-          hipMemcpyAsync(d_keys, keys, nq * sizeof(GraKeyRef),
+          hipMemcpyAsync(mg.d_keys, keys, nq * sizeof(GraKeyRef),
                          hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-          hipMemcpyAsync(d_keybuf, keybuf, keybuf_len,
+          hipMemcpyAsync(mg.d_keybuf, keybuf, keybuf_len,
                          hipMemcpyHostToDevice, e->stream) != hipSuccess)
         break;
+      MgExtra *d_extra = mixed ? mg.d_extra.get() : nullptr;
       if (use_hj) {
         uint32_t nruns32 = (uint32_t)views.size();
         if (hipMemcpyAsync(mg.d_qtab, qtab.data(), qtab_size * 8,
                            hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemsetAsync(mg.d_counts, 0, 8, e->stream) != hipSuccess ||
+            hipMemsetAsync(mg.counts.d, 0, 8, e->stream) != hipSuccess ||
             hipMemsetAsync(mg.d_aux, 0, (size_t)nq * 8 * 5, e->stream) !=
                 hipSuccess)
           break;
-        uint64_t max_entries = 0;
-        for (auto &v : views)
-          max_entries = v.n_entries > max_entries ? v.n_entries : max_entries;
-        uint32_t bx = (uint32_t)((max_entries + 255) / 256);
-        if (bx > 1024) bx = 1024;
-        if (bx == 0) bx = 1;
-        hipLaunchKernelGGL(k_mg_scan, dim3(bx, nruns32), dim3(256), 0,
-                           e->stream, e->d_store, d_runs,
-                           (const uint64_t *)mg.d_qtab, qtab_size - 1, d_keys,
-                           d_keybuf, (MgCand *)mg.d_cands, mg.d_counts,
-                           cand_cap, (MgTomb *)mg.d_tombs, mg.d_counts + 1,
+        hipLaunchKernelGGL(k_mg_scan,
+                           dim3(longest_run_blocks(views, 1024), nruns32),
+                           dim3(256), 0, e->stream, e->d_store, mg.d_runs,
+                           mg.d_qtab, qtab_size - 1, mg.d_keys, mg.d_keybuf,
+                           mg.d_cands, d_ncand, cand_cap, mg.d_tombs, d_ntomb,
                            tomb_cap);
         if (hipGetLastError() != hipSuccess) break;
-        unsigned long long *aux = (unsigned long long *)mg.d_aux;
+        unsigned long long *aux = mg.d_aux;
         unsigned long long *term_pack = aux, *mergeq = aux + nq,
                            *rdq = aux + 2 * nq, *winner = aux + 3 * nq,
                            *accq = aux + 4 * (size_t)nq;
         uint32_t rb = (cand_cap + 255) / 256;
         hipLaunchKernelGGL(k_mg_resolve1, dim3(rb), dim3(256), 0, e->stream,
-                           (MgCand *)mg.d_cands, mg.d_counts, cand_cap,
-                           term_pack, mergeq);
+                           mg.d_cands, d_ncand, cand_cap, term_pack, mergeq);
         hipLaunchKernelGGL(k_mg_tombs, dim3((nq + 255) / 256), dim3(256), 0,
-                           e->stream, e->d_store, d_runs,
-                           (MgTomb *)mg.d_tombs, mg.d_counts + 1, tomb_cap,
-                           d_keys, d_keybuf, nq, rdq);
+                           e->stream, e->d_store, mg.d_runs, mg.d_tombs,
+                           d_ntomb, tomb_cap, mg.d_keys, mg.d_keybuf, nq, rdq);
         hipLaunchKernelGGL(k_mg_resolve2, dim3(rb), dim3(256), 0, e->stream,
-                           (MgCand *)mg.d_cands, mg.d_counts, cand_cap,
-                           term_pack, winner);
+                           mg.d_cands, d_ncand, cand_cap, term_pack, winner);
         if (fold_u64) /* after resolve1 and tombs: needs T and RD */
           hipLaunchKernelGGL(k_mg_fold, dim3(rb), dim3(256), 0, e->stream,
-                             e->d_store, d_runs, (MgCand *)mg.d_cands,
-                             mg.d_counts, cand_cap, term_pack, rdq, accq);
+                             e->d_store, mg.d_runs, mg.d_cands, d_ncand,
+                             cand_cap, term_pack, rdq, accq);
         hipLaunchKernelGGL(k_mg_emit, dim3(nq), dim3(64), 0, e->stream,
-                           e->d_store, d_runs, term_pack, mergeq, rdq, winner,
-                           nq, d_valbuf, val_stride, d_out,
-                           mixed ? (MgExtra *)mg.d_extra : nullptr,
+                           e->d_store, mg.d_runs, term_pack, mergeq, rdq,
+                           winner, nq, mg.d_valbuf, val_stride, mg.d_out,
+                           d_extra,
                            fold_u64 ? accq : (unsigned long long *)nullptr);
         if (hipGetLastError() != hipSuccess) break;
-        if (hipMemcpyAsync(mg.h_counts, mg.d_counts, 8,
+        if (hipMemcpyAsync(mg.counts.h, mg.counts.d, 8,
                            hipMemcpyDeviceToHost, e->stream) != hipSuccess)
           break;
       } else {
         hipLaunchKernelGGL(k_multiget, dim3(nq), dim3(256), 0, e->stream,
-                           e->d_store, d_runs, (uint32_t)views.size(), d_keys,
-                           d_keybuf, nq, d_valbuf, val_stride, d_out,
-                           mixed ? (MgExtra *)mg.d_extra : nullptr,
-                           fold_u64 ? 1 : 0);
+                           e->d_store, mg.d_runs, (uint32_t)views.size(),
+                           mg.d_keys, mg.d_keybuf, nq, mg.d_valbuf, val_stride,
+                           mg.d_out, d_extra, fold_u64 ? 1 : 0);
         if (hipGetLastError() != hipSuccess) break;
       }
-      if (hipMemcpyAsync(out, d_out, nq * sizeof(GraGetResult),
+      if (hipMemcpyAsync(out, mg.d_out, nq * sizeof(GraGetResult),
                          hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-          hipMemcpyAsync(valbuf, d_valbuf, vb, hipMemcpyDeviceToHost,
+          hipMemcpyAsync(valbuf, mg.d_valbuf, vb, hipMemcpyDeviceToHost,
                          e->stream) != hipSuccess)
         break;
       if (mixed) {
@@ -2580,7 +2102,7 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
       }
       if (hipStreamSynchronize(e->stream) != hipSuccess) break;
       if (use_hj &&
-          (mg.h_counts[0] > cand_cap || mg.h_counts[1] > tomb_cap))
+          (mg.counts.h->ncand > cand_cap || mg.counts.h->ntomb > tomb_cap))
         break; /* caps overflowed: results invalid, retry via scan kernel */
       rc = GRA_OK;
     } while (0);
@@ -2637,6 +2159,77 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
 
 enum { kScanTakeHostPath = 100 }; /* scan_device: not servable on device */
 
+/* The scan chain's front end, shared by gra_scan and gra_compact (both run
+ * it under e->mu on the shared ScCache): collect -> bitonic sort -> with a
+ * fold mode, heads + fold. sc_reserve_chain sizes, exactly, every buffer
+ * the chain through the prefix sum needs for `cap` candidates (a power of
+ * two >= kScTile); heads and folds only when the chain folds. */
+static bool sc_reserve_chain(GraEngine::ScCache &sc, size_t nviews,
+                             uint32_t cap, bool fold) {
+  return sc.d_runs.reserve_bytes(nviews * sizeof(RunView)) &&
+         sc.d_tombs.reserve_bytes((size_t)kScTombCap * sizeof(ScTomb)) &&
+         sc.d_cands.reserve_bytes((size_t)cap * sizeof(ScCand)) &&
+         sc.d_items.reserve_bytes((size_t)cap * sizeof(ScItem)) &&
+         sc.d_bsums.reserve_bytes(((size_t)cap / 256 + 1) * sizeof(ScSum)) &&
+         (!fold || (sc.d_heads.reserve_bytes((size_t)cap * sizeof(ScHead)) &&
+                    sc.d_folds.reserve_bytes((size_t)cap * sizeof(ScFold))));
+}
+
+/* fold_mode: 0 = no fold kernels, 1 = concat, 2 = u64add; `unbounded` is
+ * gra_compact's concat (k_sc_fold<1, true>). False when the control block or
+ * the run views could not be queued; launch errors are left for the caller's
+ * hipGetLastError at the end of its chain. */
+static bool sc_launch_front(GraEngine *e, const std::vector<RunView> &views,
+                            bool sorted0, const ScBounds &bd, uint32_t cap,
+                            int fold_mode, bool unbounded) {
+  auto &sc = e->sc;
+  const uint8_t *store = e->d_store;
+  hipStream_t st = e->stream;
+  if (hipMemsetAsync(sc.ctl.d, 0, sizeof(ScCtl), st) != hipSuccess ||
+      hipMemcpyAsync(sc.d_runs, views.data(), views.size() * sizeof(RunView),
+                     hipMemcpyHostToDevice, st) != hipSuccess)
+    return false;
+  /* grid.y = one row per run, 65535 rows a launch (gra_scan never has more:
+   * one launch) */
+  uint32_t bx = longest_run_blocks(views, 1024);
+  for (size_t first = 0; first < views.size(); first += 65535) {
+    size_t rows = views.size() - first < 65535 ? views.size() - first : 65535;
+    hipLaunchKernelGGL(k_sc_collect, dim3(bx, (uint32_t)rows), dim3(256), 0,
+                       st, store, sc.d_runs + first, bd, sc.d_cands, cap,
+                       sc.d_tombs, kScTombCap, sc.ctl.d,
+                       (sorted0 && first == 0) ? 1u : 0u);
+  }
+  /* bitonic sort, sized for the capacity: stages past the padded
+   * candidate count return at once */
+  hipLaunchKernelGGL(k_sc_sort_tile, dim3(cap / kScTile),
+                     dim3(kScTileThreads), 0, st, store, sc.d_cands, sc.ctl.d,
+                     cap, 2u, kScTile, 1);
+  for (uint32_t k = 2 * kScTile; k != 0 && k <= cap; k <<= 1) {
+    for (uint32_t j = k >> 1; j >= kScTile; j >>= 1)
+      hipLaunchKernelGGL(k_sc_sort_global, dim3(cap / 2 / 256), dim3(256), 0,
+                         st, store, sc.d_cands, sc.ctl.d, cap, j, k);
+    hipLaunchKernelGGL(k_sc_sort_tile, dim3(cap / kScTile),
+                       dim3(kScTileThreads), 0, st, store, sc.d_cands,
+                       sc.ctl.d, cap, k, k, 0);
+  }
+  if (fold_mode == 0) return true;
+  hipLaunchKernelGGL(k_sc_heads, dim3(cap / 256), dim3(256), 0, st, store,
+                     sc.d_cands, sc.d_tombs, sc.ctl.d, cap, kScTombCap,
+                     sc.d_heads, sc.d_folds);
+  uint32_t fb = cap / 4 < kScFoldWaves ? cap / 4 : kScFoldWaves;
+  if (fold_mode == 2)
+    hipLaunchKernelGGL((k_sc_fold<2>), dim3(fb / 4), dim3(256), 0, st, store,
+                       sc.d_cands, sc.d_heads, sc.ctl.d, cap, sc.d_folds);
+  else if (unbounded)
+    hipLaunchKernelGGL((k_sc_fold<1, true>), dim3(fb / 4), dim3(256), 0, st,
+                       store, sc.d_cands, sc.d_heads, sc.ctl.d, cap,
+                       sc.d_folds);
+  else
+    hipLaunchKernelGGL((k_sc_fold<1>), dim3(fb / 4), dim3(256), 0, st, store,
+                       sc.d_cands, sc.d_heads, sc.ctl.d, cap, sc.d_folds);
+  return true;
+}
+
 /* Device path over a snapshot of device-resident runs. One sync to learn
  * the page size, then the result copy. Returns GRA_OK / GRA_BUF_TOO_SMALL /
  * GRA_ERR, or kScanTakeHostPath when the tombstone list overflows or staging
@@ -2653,23 +2246,8 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
   const int fold = !e->opts.fold_on_device              ? 0
                    : e->opts.merge_op == GRA_MERGE_U64ADD ? 2
                                                           : 1;
-  auto grow = [](auto **p, size_t *have, size_t need) {
-    if (*have >= need) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, need) != hipSuccess) {
-      (void)hipGetLastError(); /* out of memory is handled: host path */
-      return false;
-    }
-    *have = need;
-    return true;
-  };
-  uint64_t total_entries = 0, max_run = 0;
-  for (const auto &v : views) {
-    total_entries += v.n_entries;
-    max_run = v.n_entries > max_run ? v.n_entries : max_run;
-  }
+  uint64_t total_entries = 0;
+  for (const auto &v : views) total_entries += v.n_entries;
   /* a page never holds more than the shard does, whatever the caller's
    * max_entries / cap */
   uint64_t ent_cap = max_entries < total_entries ? max_entries : total_entries;
@@ -2689,26 +2267,10 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
     for (uint32_t i = 0; i < 8; i++) v = (v << 8) | (i < n ? p[i] : 0);
     return v;
   };
-  if (!sc.d_ctl) {
-    if (hipMalloc(&sc.d_ctl, sizeof(ScCtl)) != hipSuccess) {
-      (void)hipGetLastError();
-      sc.d_ctl = nullptr;
-      return kScanTakeHostPath;
-    }
-    if (hipHostMalloc(&sc.h_ctl, sizeof(ScCtl)) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(sc.d_ctl);
-      sc.d_ctl = nullptr;
-      sc.h_ctl = nullptr;
-      return kScanTakeHostPath;
-    }
-  }
-  if (!grow(&sc.d_runs, &sc.runs_cap, views.size() * sizeof(RunView)) ||
-      !grow(&sc.d_bounds, &sc.bounds_cap, hb.size()) ||
-      !grow(&sc.d_tombs, &sc.tombs_cap, (size_t)kScTombCap * sizeof(ScTomb)) ||
-      !grow(&sc.d_ents, &sc.ents_cap,
-            (size_t)ent_cap * sizeof(GraScanEntry) + 16) ||
-      !grow(&sc.d_out, &sc.out_cap, (size_t)out_cap + 16))
+  /* out of memory is handled: host path */
+  if (!sc.ctl.ensure() || !sc.d_bounds.reserve_bytes(hb.size()) ||
+      !sc.d_ents.reserve_bytes((size_t)ent_cap * sizeof(GraScanEntry) + 16) ||
+      !sc.d_out.reserve_bytes((size_t)out_cap + 16))
     return kScanTakeHostPath;
   ScBounds bd = {};
   bd.lo = sc.d_bounds;
@@ -2719,92 +2281,49 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
   bd.hi_len = hi_len;
   bd.has_hi = has_hi ? 1 : 0;
   uint32_t cand_cap = sc.cand_cap ? sc.cand_cap : kScFirstCap;
-  uint32_t bx = (uint32_t)((max_run + 255) / 256);
-  if (bx > 1024) bx = 1024;
-  if (bx == 0) bx = 1;
   const uint8_t *store = e->d_store;
   hipStream_t st = e->stream;
   for (int attempt = 0;; attempt++) {
     uint32_t nblocks = cand_cap / 256;
-    if (!grow(&sc.d_cands, &sc.cands_cap, (size_t)cand_cap * sizeof(ScCand)) ||
-        !grow(&sc.d_items, &sc.items_cap, (size_t)cand_cap * sizeof(ScItem)) ||
-        !grow(&sc.d_bsums, &sc.bsums_cap,
-              ((size_t)nblocks + 1) * sizeof(ScSum)) ||
-        (fold &&
-         (!grow(&sc.d_heads, &sc.heads_cap, (size_t)cand_cap * sizeof(ScHead)) ||
-          !grow(&sc.d_folds, &sc.folds_cap,
-                (size_t)cand_cap * sizeof(ScFold)))))
+    if (!sc_reserve_chain(sc, views.size(), cand_cap, fold != 0))
       return kScanTakeHostPath;
     sc.cand_cap = cand_cap;
     bool ok = false;
     do {
-      if (hipMemsetAsync(sc.d_ctl, 0, sizeof(ScCtl), st) != hipSuccess ||
-          hipMemcpyAsync(sc.d_runs, views.data(),
-                         views.size() * sizeof(RunView),
+      /* fold_on_device folds the merge chains in the front end: their sizes
+       * feed the prefix sum */
+      if (hipMemcpyAsync(sc.d_bounds, hb.data(), hb.size(),
                          hipMemcpyHostToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(sc.d_bounds, hb.data(), hb.size(),
-                         hipMemcpyHostToDevice, st) != hipSuccess)
+          !sc_launch_front(e, views, sorted0, bd, cand_cap, fold, false))
         break;
-      hipLaunchKernelGGL(k_sc_collect, dim3(bx, (uint32_t)views.size()),
-                         dim3(256), 0, st, store, sc.d_runs, bd, sc.d_cands,
-                         cand_cap, sc.d_tombs, kScTombCap, sc.d_ctl,
-                         sorted0 ? 1u : 0u);
-      /* bitonic sort, sized for the capacity: stages past the padded
-       * candidate count return at once */
-      hipLaunchKernelGGL(k_sc_sort_tile, dim3(cand_cap / kScTile),
-                         dim3(kScTileThreads), 0, st, store, sc.d_cands,
-                         sc.d_ctl, cand_cap, 2u, kScTile, 1);
-      for (uint32_t k = 2 * kScTile; k != 0 && k <= cand_cap; k <<= 1) {
-        for (uint32_t j = k >> 1; j >= kScTile; j >>= 1)
-          hipLaunchKernelGGL(k_sc_sort_global, dim3(cand_cap / 2 / 256),
-                             dim3(256), 0, st, store, sc.d_cands, sc.d_ctl,
-                             cand_cap, j, k);
-        hipLaunchKernelGGL(k_sc_sort_tile, dim3(cand_cap / kScTile),
-                           dim3(kScTileThreads), 0, st, store, sc.d_cands,
-                           sc.d_ctl, cand_cap, k, k, 0);
-      }
-      if (fold) {
-        /* fold the merge chains first: their sizes feed the prefix sum */
-        hipLaunchKernelGGL(k_sc_heads, dim3(nblocks), dim3(256), 0, st, store,
-                           sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
-                           kScTombCap, sc.d_heads, sc.d_folds);
-        uint32_t fb = cand_cap / 4 < kScFoldWaves ? cand_cap / 4 : kScFoldWaves;
-        if (fold == 2)
-          hipLaunchKernelGGL(k_sc_fold<2>, dim3(fb / 4), dim3(256), 0, st,
-                             store, sc.d_cands, sc.d_heads, sc.d_ctl, cand_cap,
-                             sc.d_folds);
-        else
-          hipLaunchKernelGGL(k_sc_fold<1>, dim3(fb / 4), dim3(256), 0, st,
-                             store, sc.d_cands, sc.d_heads, sc.d_ctl, cand_cap,
-                             sc.d_folds);
+      if (fold)
         hipLaunchKernelGGL(k_sc_resolve<true>, dim3(nblocks), dim3(256), 0, st,
-                           store, sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
+                           store, sc.d_cands, sc.d_tombs, sc.ctl.d, cand_cap,
                            kScTombCap, sc.d_items, sc.d_bsums, sc.d_folds);
-      } else {
+      else
         hipLaunchKernelGGL(k_sc_resolve<false>, dim3(nblocks), dim3(256), 0, st,
-                           store, sc.d_cands, sc.d_tombs, sc.d_ctl, cand_cap,
+                           store, sc.d_cands, sc.d_tombs, sc.ctl.d, cand_cap,
                            kScTombCap, sc.d_items, sc.d_bsums,
                            (const ScFold *)nullptr);
-      }
       hipLaunchKernelGGL(k_sc_scan2, dim3(1), dim3(256), 0, st, sc.d_bsums,
-                         nblocks, sc.d_ctl);
+                         nblocks, sc.ctl.d);
       if (fold == 2)
         hipLaunchKernelGGL((k_sc_emit<16, 2>), dim3(cand_cap / 16), dim3(256),
                            0, st, store, sc.d_cands, sc.d_items, sc.d_bsums,
-                           sc.d_ctl, cand_cap, max_entries, byte_cap, sc.d_out,
+                           sc.ctl.d, cand_cap, max_entries, byte_cap, sc.d_out,
                            sc.d_ents, sc.d_folds);
       else if (fold == 1)
         hipLaunchKernelGGL((k_sc_emit<16, 1>), dim3(cand_cap / 16), dim3(256),
                            0, st, store, sc.d_cands, sc.d_items, sc.d_bsums,
-                           sc.d_ctl, cand_cap, max_entries, byte_cap, sc.d_out,
+                           sc.ctl.d, cand_cap, max_entries, byte_cap, sc.d_out,
                            sc.d_ents, sc.d_folds);
       else
         hipLaunchKernelGGL((k_sc_emit<16, 0>), dim3(cand_cap / 16), dim3(256),
                            0, st, store, sc.d_cands, sc.d_items, sc.d_bsums,
-                           sc.d_ctl, cand_cap, max_entries, byte_cap, sc.d_out,
+                           sc.ctl.d, cand_cap, max_entries, byte_cap, sc.d_out,
                            sc.d_ents, (const ScFold *)nullptr);
       if (hipGetLastError() != hipSuccess) break;
-      if (hipMemcpyAsync(sc.h_ctl, sc.d_ctl, sizeof(ScCtl),
+      if (hipMemcpyAsync(sc.ctl.h, sc.ctl.d, sizeof(ScCtl),
                          hipMemcpyDeviceToHost, st) != hipSuccess ||
           hipStreamSynchronize(st) != hipSuccess)
         break;
@@ -2815,14 +2334,14 @@ static int scan_device(GraEngine *e, const std::vector<RunView> &views,
       g_err = "gra_scan: device op failed";
       return GRA_ERR;
     }
-    if (sc.h_ctl->ntomb > kScTombCap) return kScanTakeHostPath;
-    if (sc.h_ctl->ncand <= cand_cap) break;
+    if (sc.ctl.h->ntomb > kScTombCap) return kScanTakeHostPath;
+    if (sc.ctl.h->ncand <= cand_cap) break;
     /* the counter kept counting past the cap: grow to it and re-run once
      * (the snapshot is fixed, so the second count cannot differ) */
-    if (attempt > 0 || sc.h_ctl->ncand > (1u << 30)) return kScanTakeHostPath;
-    while (cand_cap < sc.h_ctl->ncand) cand_cap <<= 1;
+    if (attempt > 0 || sc.ctl.h->ncand > (1u << 30)) return kScanTakeHostPath;
+    while (cand_cap < sc.ctl.h->ncand) cand_cap <<= 1;
   }
-  const ScCtl &r = *sc.h_ctl;
+  const ScCtl &r = *sc.ctl.h;
   info->candidates = r.ncand;
   if (r.too_small) return GRA_BUF_TOO_SMALL;
   /* only the emitted entries and bytes cross PCIe */
@@ -2875,8 +2394,7 @@ int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
       else {
         /* at most one sorted run, and it is the shard's oldest */
         if (views.empty() && rp->sorted) sorted0 = true;
-        views.push_back({rp->hdr_cur, rp->payload_cur, rp->n_entries,
-                         rp->pay_rel_base});
+        views.push_back(view_of(*rp));
         dev_payload += rp->payload_bytes;
       }
     }
@@ -2933,58 +2451,14 @@ static int compact_device(GraEngine *e, const std::vector<RunView> &views,
                           bool sorted0, uint64_t total_entries, CpCtl *res) {
   std::lock_guard<std::mutex> lk_engine(e->mu);
   auto &sc = e->sc;
-  auto grow = [](auto **p, size_t *have, size_t need) {
-    if (*have >= need) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc(p, need) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    *have = need;
-    return true;
-  };
   const int mode = e->opts.merge_op == GRA_MERGE_U64ADD ? 2 : 1;
   uint32_t cap = kScTile; /* power of two >= the prefix's entries */
   while (cap < total_entries) cap <<= 1;
   uint32_t nblocks = cap / 256;
-  uint64_t max_run = 0;
-  for (const auto &v : views)
-    max_run = v.n_entries > max_run ? v.n_entries : max_run;
-  uint32_t bx = (uint32_t)((max_run + 255) / 256);
-  if (bx > 1024) bx = 1024;
-  if (bx == 0) bx = 1;
-  bool ok = true;
-  if (!sc.d_ctl) {
-    ok = hipMalloc(&sc.d_ctl, sizeof(ScCtl)) == hipSuccess;
-    if (ok && hipHostMalloc(&sc.h_ctl, sizeof(ScCtl)) != hipSuccess) {
-      (void)hipFree(sc.d_ctl);
-      sc.h_ctl = nullptr;
-      ok = false;
-    }
-    if (!ok) sc.d_ctl = nullptr;
-  }
-  if (ok && !sc.d_cp) {
-    ok = hipMalloc(&sc.d_cp, sizeof(CpCtl)) == hipSuccess;
-    if (ok && hipHostMalloc(&sc.h_cp, sizeof(CpCtl)) != hipSuccess) {
-      (void)hipFree(sc.d_cp);
-      sc.h_cp = nullptr;
-      ok = false;
-    }
-    if (!ok) sc.d_cp = nullptr;
-  }
   /* the scan's buffers are shared (both run under e->mu); sc.cand_cap, the
    * capacity gra_scan sizes its launches by, is left alone */
-  if (!ok || !grow(&sc.d_runs, &sc.runs_cap, views.size() * sizeof(RunView)) ||
-      !grow(&sc.d_bounds, &sc.bounds_cap, 64) ||
-      !grow(&sc.d_tombs, &sc.tombs_cap, (size_t)kScTombCap * sizeof(ScTomb)) ||
-      !grow(&sc.d_cands, &sc.cands_cap, (size_t)cap * sizeof(ScCand)) ||
-      !grow(&sc.d_items, &sc.items_cap, (size_t)cap * sizeof(ScItem)) ||
-      !grow(&sc.d_bsums, &sc.bsums_cap, ((size_t)nblocks + 1) * sizeof(ScSum)) ||
-      !grow(&sc.d_heads, &sc.heads_cap, (size_t)cap * sizeof(ScHead)) ||
-      !grow(&sc.d_folds, &sc.folds_cap, (size_t)cap * sizeof(ScFold))) {
-    (void)hipGetLastError();
+  if (!sc.ctl.ensure() || !sc.cp.ensure() || !sc.d_bounds.reserve_bytes(64) ||
+      !sc_reserve_chain(sc, views.size(), cap, true)) {
     g_err = "gra_compact: device staging allocation failed";
     return GRA_ERR;
   }
@@ -2992,63 +2466,33 @@ static int compact_device(GraEngine *e, const std::vector<RunView> &views,
   bd.lo = bd.hi = sc.d_bounds;
   uint8_t *store = e->d_store;
   hipStream_t st = e->stream;
-  ok = false;
+  bool ok = false;
   do {
-    if (hipMemsetAsync(sc.d_ctl, 0, sizeof(ScCtl), st) != hipSuccess ||
-        hipMemsetAsync(sc.d_cp, 0, sizeof(CpCtl), st) != hipSuccess ||
-        hipMemcpyAsync(sc.d_runs, views.data(), views.size() * sizeof(RunView),
-                       hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemsetAsync(sc.cp.d, 0, sizeof(CpCtl), st) != hipSuccess ||
+        !sc_launch_front(e, views, sorted0, bd, cap, mode, true))
       break;
-    /* grid.y = one row per run, 65535 rows a launch */
-    for (size_t first = 0; first < views.size(); first += 65535) {
-      size_t rows = views.size() - first < 65535 ? views.size() - first : 65535;
-      hipLaunchKernelGGL(k_sc_collect, dim3(bx, (uint32_t)rows), dim3(256), 0,
-                         st, store, sc.d_runs + first, bd, sc.d_cands, cap,
-                         sc.d_tombs, kScTombCap, sc.d_ctl,
-                         (sorted0 && first == 0) ? 1u : 0u);
-    }
-    hipLaunchKernelGGL(k_sc_sort_tile, dim3(cap / kScTile),
-                       dim3(kScTileThreads), 0, st, store, sc.d_cands, sc.d_ctl,
-                       cap, 2u, kScTile, 1);
-    for (uint32_t k = 2 * kScTile; k != 0 && k <= cap; k <<= 1) {
-      for (uint32_t j = k >> 1; j >= kScTile; j >>= 1)
-        hipLaunchKernelGGL(k_sc_sort_global, dim3(cap / 2 / 256), dim3(256), 0,
-                           st, store, sc.d_cands, sc.d_ctl, cap, j, k);
-      hipLaunchKernelGGL(k_sc_sort_tile, dim3(cap / kScTile),
-                         dim3(kScTileThreads), 0, st, store, sc.d_cands,
-                         sc.d_ctl, cap, k, k, 0);
-    }
-    hipLaunchKernelGGL(k_sc_heads, dim3(nblocks), dim3(256), 0, st, store,
-                       sc.d_cands, sc.d_tombs, sc.d_ctl, cap, kScTombCap,
-                       sc.d_heads, sc.d_folds);
-    uint32_t fb = cap / 4 < kScFoldWaves ? cap / 4 : kScFoldWaves;
-    if (mode == 2)
-      hipLaunchKernelGGL((k_sc_fold<2>), dim3(fb / 4), dim3(256), 0, st, store,
-                         sc.d_cands, sc.d_heads, sc.d_ctl, cap, sc.d_folds);
-    else
-      hipLaunchKernelGGL((k_sc_fold<1, true>), dim3(fb / 4), dim3(256), 0, st,
-                         store, sc.d_cands, sc.d_heads, sc.d_ctl, cap,
-                         sc.d_folds);
     hipLaunchKernelGGL(k_cp_resolve, dim3(nblocks), dim3(256), 0, st, store,
-                       sc.d_cands, sc.d_tombs, sc.d_ctl, cap, kScTombCap,
-                       sc.d_items, sc.d_bsums, sc.d_folds, sc.d_cp);
+                       sc.d_cands, sc.d_tombs, sc.ctl.d, cap, kScTombCap,
+                       sc.d_items, sc.d_bsums, sc.d_folds, sc.cp.d);
     hipLaunchKernelGGL(k_cp_finish, dim3(1), dim3(256), 0, st, sc.d_bsums,
-                       nblocks, sc.d_ctl, cap, kScTombCap, e->d_cursor,
-                       (uint64_t)e->opts.store_bytes, sc.d_cp);
+                       nblocks, sc.ctl.d, cap, kScTombCap, e->d_cursor,
+                       (uint64_t)e->opts.store_bytes, sc.cp.d);
     if (mode == 2) {
       hipLaunchKernelGGL((k_cp_emit<16, 2>), dim3(cap / 16), dim3(256), 0, st,
-                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.d_ctl,
-                         sc.d_cp, cap, sc.d_folds);
+                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.ctl.d,
+                         sc.cp.d, cap, sc.d_folds);
     } else {
+      /* the grid k_sc_fold ran on: one wave per listed head, strided */
+      uint32_t fb = cap / 4 < kScFoldWaves ? cap / 4 : kScFoldWaves;
       hipLaunchKernelGGL((k_cp_emit<16, 1>), dim3(cap / 16), dim3(256), 0, st,
-                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.d_ctl,
-                         sc.d_cp, cap, sc.d_folds);
+                         store, sc.d_cands, sc.d_items, sc.d_bsums, sc.ctl.d,
+                         sc.cp.d, cap, sc.d_folds);
       hipLaunchKernelGGL(k_cp_emit_chain, dim3(fb / 4), dim3(256), 0, st, store,
                          sc.d_cands, sc.d_items, sc.d_bsums, sc.d_heads,
-                         sc.d_ctl, sc.d_cp, cap, sc.d_folds);
+                         sc.ctl.d, sc.cp.d, cap, sc.d_folds);
     }
     if (hipGetLastError() != hipSuccess) break;
-    if (hipMemcpyAsync(sc.h_cp, sc.d_cp, sizeof(CpCtl), hipMemcpyDeviceToHost,
+    if (hipMemcpyAsync(sc.cp.h, sc.cp.d, sizeof(CpCtl), hipMemcpyDeviceToHost,
                        st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
       break;
@@ -3059,7 +2503,7 @@ static int compact_device(GraEngine *e, const std::vector<RunView> &views,
     g_err = "gra_compact: device op failed";
     return GRA_ERR;
   }
-  *res = *sc.h_cp;
+  *res = *sc.cp.h;
   return GRA_OK;
 }
 
@@ -3090,8 +2534,7 @@ int gra_compact(GraDb *db, GraCompactInfo *info) {
   std::vector<RunView> views;
   for (const auto &rp : snap) {
     if (rp->n_entries == 0) continue;
-    views.push_back(
-        {rp->hdr_cur, rp->payload_cur, rp->n_entries, rp->pay_rel_base});
+    views.push_back(view_of(*rp));
     info->entries_in += rp->n_entries;
     info->bytes_in +=
         (uint64_t)rp->n_entries * sizeof(wb::RecHdr) + rp->payload_bytes;
@@ -3165,7 +2608,7 @@ int gra_shard_checksum(GraDb *db, uint64_t *out) {
                                   h[i].val_len, pay + h[i].kv_off,
                                   pay + h[i].kv_off + h[i].key_len);
       } else {
-        views.push_back({r.hdr_cur, r.payload_cur, r.n_entries, r.pay_rel_base});
+        views.push_back(view_of(r));
       }
     }
   }
@@ -3174,32 +2617,28 @@ int gra_shard_checksum(GraDb *db, uint64_t *out) {
     return GRA_OK;
   }
   std::lock_guard<std::mutex> lk(e->mu);
-  RunView *d_runs = nullptr;
-  unsigned long long *d_sum = nullptr;
-  int rc = GRA_ERR;
-  do {
-    if (hipMalloc(&d_runs, views.size() * sizeof(RunView)) != hipSuccess ||
-        hipMalloc(&d_sum, 8) != hipSuccess)
-      break;
-    if (hipMemcpy(d_runs, views.data(), views.size() * sizeof(RunView),
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(d_sum, 0, 8) != hipSuccess)
-      break;
-    uint32_t nb = views.size() < 1024 ? (uint32_t)views.size() : 1024;
-    hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(256), 0, e->stream, e->d_store,
-                       d_runs, (uint32_t)views.size(), d_sum);
-    if (hipGetLastError() != hipSuccess) break;
-    unsigned long long sum = 0;
-    if (hipStreamSynchronize(e->stream) != hipSuccess ||
-        hipMemcpy(&sum, d_sum, 8, hipMemcpyDeviceToHost) != hipSuccess)
-      break;
-    *out = host_sum + (uint64_t)sum;
-    rc = GRA_OK;
-  } while (0);
-  if (rc != GRA_OK) g_err = "gra_shard_checksum: device op failed";
-  if (d_runs) (void)hipFree(d_runs);
-  if (d_sum) (void)hipFree(d_sum);
-  return rc;
+  DevBuf<RunView> d_runs; /* per call: freed on every return */
+  DevBuf<unsigned long long> d_sum;
+  uint32_t nb = views.size() < 1024 ? (uint32_t)views.size() : 1024;
+  unsigned long long sum = 0;
+  bool ok = d_runs.reserve_bytes(views.size() * sizeof(RunView)) &&
+            d_sum.reserve_bytes(8) &&
+            hipMemcpy(d_runs, views.data(), views.size() * sizeof(RunView),
+                      hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemset(d_sum, 0, 8) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_checksum, dim3(nb), dim3(256), 0, e->stream,
+                       e->d_store, d_runs, (uint32_t)views.size(), d_sum);
+    ok = hipGetLastError() == hipSuccess &&
+         hipStreamSynchronize(e->stream) == hipSuccess &&
+         hipMemcpy(&sum, d_sum, 8, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  if (!ok) {
+    g_err = "gra_shard_checksum: device op failed";
+    return GRA_ERR;
+  }
+  *out = host_sum + (uint64_t)sum;
+  return GRA_OK;
 }
 
 int gra_pin_alloc(GraEngine *e, size_t bytes, uint8_t **ptr) {

@@ -353,6 +353,39 @@ __device__ inline bool sc_same_key(const uint8_t *store, const ScCand &a,
              0;
 }
 
+/* Is the key's newest entry covered by a range tombstone at least as new as
+ * it is? Tombstones older than the head are skipped without touching their
+ * keys. */
+__device__ inline bool sc_tomb_kills(const uint8_t *store,
+                                     const ScTomb *__restrict__ tombs,
+                                     uint32_t ntomb, const ScCand &c) {
+  const uint8_t *key = store + c.koff;
+  for (uint32_t t = 0; t < ntomb; t++) {
+    ScTomb tb = tombs[t];
+    if (tb.seq < c.seq) continue;
+    const uint8_t *b = store + tb.boff;
+    if (sc_cmp_bytes(b, tb.bl, key, c.klen) <= 0 &&
+        sc_cmp_bytes(key, c.klen, b + tb.bl, tb.el) < 0)
+      return true;
+  }
+  return false;
+}
+
+/* inclusive scan of one ScSum per thread over a block of 256 */
+__device__ inline ScSum sc_block_scan(ScSum v, ScSum *sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int ofs = 1; ofs < 256; ofs <<= 1) {
+    ScSum a = sh[threadIdx.x];
+    ScSum b = threadIdx.x >= (uint32_t)ofs ? sh[threadIdx.x - ofs]
+                                           : ScSum{0, 0, 0};
+    __syncthreads();
+    sh[threadIdx.x] = sc_add(a, b);
+    __syncthreads();
+  }
+  return sh[threadIdx.x];
+}
+
 /* ---- fold_on_device: fold merge chains before the prefix sum ----
  * Two passes in front of k_sc_resolve, launched only when the engine option
  * is set, so the default chain is the one above, kernel for kernel.
@@ -541,13 +574,7 @@ __global__ void __launch_bounds__(256) k_sc_resolve(
   ScSum v = {0, 0, 0};
   if (i < n) {
     ScCand c = cands[i];
-    bool head = i == 0;
-    if (!head) {
-      ScCand p = cands[i - 1];
-      head = p.pref != c.pref || p.klen != c.klen ||
-             sc_key_cmp_from(store + p.koff, p.klen, store + c.koff, c.klen,
-                             8) != 0;
-    }
+    bool head = i == 0 || !sc_same_key(store, cands[i - 1], c);
     if (FOLD && head && c.type == wb::kMerge) {
       ScFold f = folds[i];
       if (f.flags & kScFoldLive) {
@@ -555,38 +582,17 @@ __global__ void __launch_bounds__(256) k_sc_resolve(
         v.bytes = (uint64_t)c.klen + ((f.flags & kScFoldFolded) ? f.vlen : 0u);
       }
     } else if (head && (c.type == wb::kValue || c.type == wb::kMerge)) {
-      const uint8_t *key = store + c.koff;
-      bool live = true;
-      for (uint32_t t = 0; t < ntomb && live; t++) {
-        ScTomb tb = tombs[t];
-        if (tb.seq < c.seq) continue;
-        const uint8_t *b = store + tb.boff;
-        if (sc_cmp_bytes(b, tb.bl, key, c.klen) <= 0 &&
-            sc_cmp_bytes(key, c.klen, b + tb.bl, tb.el) < 0)
-          live = false;
-      }
-      if (live) {
+      if (!sc_tomb_kills(store, tombs, ntomb, c)) {
         v.cnt = 1;
         v.bytes = (uint64_t)c.klen + (c.type == wb::kValue ? c.vlen : 0u);
       }
     }
   }
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (int ofs = 1; ofs < 256; ofs <<= 1) {
-    ScSum a = sh[threadIdx.x];
-    ScSum b = threadIdx.x >= (uint32_t)ofs ? sh[threadIdx.x - ofs]
-                                           : ScSum{0, 0, 0};
-    __syncthreads();
-    sh[threadIdx.x] = sc_add(a, b);
-    __syncthreads();
-  }
-  if (i < n) {
-    ScSum inc = sh[threadIdx.x];
+  ScSum inc = sc_block_scan(v, sh);
+  if (i < n)
     items[i] = {inc.bytes - v.bytes, (inc.cnt - v.cnt) | (v.cnt << 31),
                 (uint32_t)v.bytes};
-  }
-  if (threadIdx.x == 255) bsums[blockIdx.x] = sh[255];
+  if (threadIdx.x == 255) bsums[blockIdx.x] = inc;
 }
 
 /* single block: block sums -> exclusive in place, with a carry across
@@ -602,17 +608,7 @@ __global__ void __launch_bounds__(256) k_sc_scan2(ScSum *__restrict__ bsums,
   for (uint32_t base = 0; base < nblocks; base += 256) {
     uint32_t i = base + threadIdx.x;
     ScSum v = i < nblocks ? bsums[i] : ScSum{0, 0, 0};
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int ofs = 1; ofs < 256; ofs <<= 1) {
-      ScSum a = sh[threadIdx.x];
-      ScSum b = threadIdx.x >= (uint32_t)ofs ? sh[threadIdx.x - ofs]
-                                             : ScSum{0, 0, 0};
-      __syncthreads();
-      sh[threadIdx.x] = sc_add(a, b);
-      __syncthreads();
-    }
-    ScSum inc = sc_add(sh[threadIdx.x], carry);
+    ScSum inc = sc_add(sc_block_scan(v, sh), carry);
     if (i < nblocks) bsums[i] = {inc.bytes - v.bytes, inc.cnt - v.cnt, 0};
     __syncthreads();
     if (threadIdx.x == 255) carry = inc;

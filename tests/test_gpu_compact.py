@@ -295,6 +295,62 @@ def test_compact_size_boundaries(olib):
     e.close()
 
 
+@pytest.mark.parametrize("fold", [0, 1])
+def test_scan_and_compact_share_staging(olib, fold):
+    """gra_compact grows the staging buffers it shares with gra_scan past the
+    capacity the scan sizes its launches by, between two scans; multiget
+    batches grow, then shrink, on the same engine."""
+    n = 20000
+    e = ra.Engine(nshards=2, fold_on_device=fold, **SMALL_ENGINE)
+    ost = oracle_ffi.Store(olib, 2)
+    small, big = e.open(0), e.open(1)
+    few = [k12(2 * i) for i in (1, 2, 3)]
+    b = PyBatch()
+    for i, k in enumerate(few):
+        b.put(k, struct.pack("<I", i))
+    apply_all(e, small, ost, [b.data()], shard=0)
+
+    def scan_small():
+        ents, sinfo = one_shot(small)
+        assert sinfo.served_by == ra.GRA_SCAN_DEVICE
+        assert len(ents) == 3 and ents == ss.expected(ost, 0, few, b"", None)
+
+    scan_small()  # the scan's candidate capacity is now its first: 16384
+    order = list(range(1, n + 1))
+    random.Random(n).shuffle(order)
+    reps = []
+    for first in range(0, n, 1000):
+        b = PyBatch()
+        for i in order[first:first + 1000]:
+            b.put(k12(2 * i), struct.pack("<I", i))
+        reps.append(b.data())
+    apply_all(e, big, ost, reps, flush_every=5, shard=1)  # 4 runs
+    universe = [k12(2 * i) for i in range(1, n + 1)]
+    info = big.compact()  # sized for 32768 candidates
+    assert info.status == ra.GRA_COMPACT_DONE
+    assert info.runs_in == 4 and info.entries_out == n
+    scan_small()
+    ents, sinfo = one_shot(big)  # 20000 > 16384: the scan's own regrow pass
+    assert sinfo.candidates == n
+    assert sinfo.served_by == ra.GRA_SCAN_DEVICE_INDEXED
+    assert [k for k, _ in ents] == sorted(k for k, _ in ents)
+    assert ents == ss.expected(ost, 1, universe, b"", None)
+    lo, hi = k12(2 * 7001), k12(2 * 7004)
+    ents, sinfo = one_shot(big, lo, hi)
+    assert len(ents) == 3 and ents == ss.expected(ost, 1, universe, lo, hi)
+    for s, db in enumerate((small, big)):
+        assert db.checksum() == olib.orc_shard_checksum(ost.h, s)
+    for first, count in ((9000, 4096), (123, 7)):  # stored and absent keys
+        keys = [k12(j) for j in range(first, first + count)]
+        for k, (st, _, val) in zip(keys, big.multiget_raw(keys)):
+            want = ost.get(1, k)
+            if want is None:
+                assert st == ra.ffi.GRA_GET_MISS, k
+            else:
+                assert st == ra.ffi.GRA_GET_FOUND and val == want, k
+    e.close()
+
+
 # 5 ------------------------------------------------------------------ chains
 
 U64_CHAINS = (1, 63, 64, 65, 320, 4000)
