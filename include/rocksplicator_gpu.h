@@ -259,10 +259,10 @@ int gra_scan(GraDb *db, const void *lo, size_t lo_len, const void *hi,
  *                            would reach 0xFFFF0000 bytes; store untouched.
  * Returns GRA_OK with one of these, GRA_ERR on a store_ring engine (it keeps
  * no runs), or GRA_FULL when the arena cannot hold the output; the store is
- * untouched then too. LIMIT: the arena is a bump allocator, so the space of
- * the replaced runs is NOT reclaimed — a compaction needs room for its
- * output on top of its input. bytes_in / bytes_out (header + payload bytes)
- * say what a later reclaim would free. */
+ * untouched then too. LIMIT: the arena is a bump allocator, so a compaction
+ * needs room for its output on top of its input; the space of the replaced
+ * runs comes back with the next gra_reclaim (below), not before. bytes_in /
+ * bytes_out (header + payload bytes) say what that reclaim will free. */
 enum { GRA_COMPACT_DONE = 0, GRA_COMPACT_NOTHING = 1, GRA_COMPACT_UNSUPPORTED = 2 };
 typedef struct {
   uint32_t status;               /* GRA_COMPACT_* */
@@ -273,6 +273,68 @@ typedef struct {
   uint64_t bytes_in, bytes_out;  /* header + payload bytes, in and out */
 } GraCompactInfo;
 int gra_compact(GraDb *db, GraCompactInfo *info);
+
+/* How full the device run arena is. `used` is the bump cursor, read with a
+ * stream-ordered copy behind the ticks already enqueued: bytes no tick or
+ * compaction can get any more. `live` is what the shards' lists still point
+ * at: header + payload bytes of every device-resident run (a truncated run
+ * counts its payload's upper bound). used - live is about what gra_reclaim
+ * would free (alignment padding stays). The call does not flush: updates
+ * staged but not yet ticked are in neither figure. On a store_ring engine
+ * `used` is the ring's monotonic cursor and `live` is 0. */
+typedef struct {
+  uint64_t capacity;  /* opts.store_bytes */
+  uint64_t used;      /* the bump cursor */
+  uint64_t live;      /* bytes of the device-resident runs the shards list */
+} GraStoreUsage;
+int gra_store_usage(GraEngine *e, GraStoreUsage *out);
+
+/* Give the arena its dead space back: every live device-resident run of
+ * every shard is slid down to the bottom of the arena, in address order, and
+ * the bump cursor is reset to the end of the last one, so the apply path and
+ * later compactions can use what replaced runs (gra_compact), dropped groups
+ * and alignment slack held. A stop-the-world pass: the call flushes first
+ * (gra_flush), holds the engine for its whole duration, and excludes
+ * gra_compact; reads and ticks issued meanwhile wait. No read result and no
+ * shard checksum changes: bytes keep their values, only their place (every
+ * segment keeps its offset mod 16, so all readers meet the alignment they met
+ * before). Host-origin runs (leader writes, drained arenas of a ring engine)
+ * are not in the arena and are left alone; the device runs of a drain_host
+ * non-ring engine move like any other, their host spans stay.
+ *
+ * info->status:
+ *   GRA_RECLAIM_DONE     used_after < used_before. bytes_moved may be 0
+ *                        (only the tail was dead);
+ *   GRA_RECLAIM_NOTHING  empty store, or already dense: store untouched,
+ *                        used_after == used_before.
+ * Returns GRA_OK with one of these. GRA_ERR on a store_ring engine (it keeps
+ * no runs), when the run list is inconsistent (overlapping runs, a run past
+ * the cursor) or when staging cannot be allocated: all of that is checked
+ * before the first copy is launched, and the store is untouched. A HIP error
+ * AFTER the first launch leaves the arena half moved, its contents undefined:
+ * the call returns GRA_ERR, gra_last_error says so, and the engine must be
+ * destroyed.
+ *
+ * LIMITS. A compaction still needs room for its output BEFORE the reclaim:
+ * compact and reclaim at a high-water mark read from gra_store_usage, not
+ * when the arena is full. An arena that is full of live data cannot be
+ * helped. Not concurrent with ticks; no ring stores. Everything above the first
+ * dead byte moves, every time; behind a hole smaller than a piece it moves
+ * through the bounce buffer, at twice the traffic. The copy sizes (bounce
+ * buffer 64 MiB, allocated at the first call that needs it; pieces of
+ * 16 MiB) can be overridden with GRA_RECLAIM_BOUNCE / GRA_RECLAIM_PIECE,
+ * byte counts read at engine creation — for tests. */
+enum { GRA_RECLAIM_DONE = 0, GRA_RECLAIM_NOTHING = 1 };
+typedef struct {
+  uint32_t status;        /* GRA_RECLAIM_* */
+  uint32_t runs_moved;    /* runs with at least one segment whose offset changed */
+  uint32_t batches;       /* copy batches launched */
+  uint32_t _pad;
+  uint64_t used_before, used_after; /* cursor before / after */
+  uint64_t bytes_moved;   /* bytes of segments whose offset changed */
+  uint64_t bytes_bounced; /* of those, moved through the bounce buffer */
+} GraReclaimInfo;
+int gra_reclaim(GraEngine *e, GraReclaimInfo *info);
 
 /* Full-store content checksum for any-size parity ("checksum of
  * checksums"): per record FNV-1a over (seq LE8 | type | key_len LE4 |

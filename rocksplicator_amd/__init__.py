@@ -25,6 +25,10 @@ from .ffi import (  # noqa: F401
     GRA_COMPACT_NOTHING,
     GRA_COMPACT_UNSUPPORTED,
     GraCompactInfo,
+    GRA_RECLAIM_DONE,
+    GRA_RECLAIM_NOTHING,
+    GraReclaimInfo,
+    GraStoreUsage,
     StoreFullError,
     MERGE_CONCAT,
     MERGE_U64ADD,

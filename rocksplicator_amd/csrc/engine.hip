@@ -23,8 +23,8 @@
  * (seq accounting per rocksdb_assumption_test.cpp:136-187).
  *
  * The device read paths keep their kernels in headers included below inside
- * namespace gra (mg_kernels.h, scan_kernels.h, compact_kernels.h) and their
- * host drivers here; their staging buffers are dev_buf.h's owning types.
+ * namespace gra (mg_kernels.h, scan_kernels.h, compact_kernels.h,
+ * reclaim_kernels.h) and their host drivers here; their staging buffers are dev_buf.h's owning types.
  *
  * No CPU fallback exists for this path: engine creation fails loudly
  * without a HIP device.
@@ -472,6 +472,9 @@ __global__ void k_rundesc(const GroupDesc *__restrict__ groups, uint32_t ngroups
 /* ---------------- device run compaction (gra_compact) ---------------- */
 #include "compact_kernels.h"
 
+/* ---------------- arena reclaim (gra_reclaim) ---------------- */
+#include "reclaim_kernels.h"
+
 /* ---- full-store checksum (parity at any size) ----
  * Same record hash as the oracle's orc_shard_checksum: FNV-1a over
  * (seq LE8 | type | key_len LE4 | val_len LE4 | key | val), u64-ADD
@@ -746,6 +749,29 @@ struct GraEngine {
   std::vector<ShardState> shards;
   Stats stats;
   std::mutex mu; /* engine-level: staging + tick enqueue + ingest */
+  /* Arena maintenance. gra_reclaim moves the bytes of every listed device
+   * run and rewrites hdr_cur / payload_cur, so an offset read under ss.mu is
+   * only good while no reclaim has run since. The rule for every reader that
+   * hands store offsets to a kernel or a copy:
+   *  - load store_epoch, snapshot the shard under ss.mu, take mu, compare;
+   *    when the epoch moved, drop mu and snapshot again (a whole new
+   *    snapshot: a run a compaction unlisted is not moved, and its bytes are
+   *    overwritten). With mu held no reclaim runs, so an unchanged epoch
+   *    vouches for the snapshot until mu is released;
+   *  - or snapshot under ss.mu with mu already held (lock order mu -> ss.mu,
+   *    the ingest path's).
+   * gra_reclaim bumps store_epoch AFTER the last shard's offsets are
+   * rewritten: bumped first, a reader could pair the new epoch with an old
+   * offset. gra_compact carries the offsets of its unlisted output run
+   * across two releases of mu, so it and gra_reclaim exclude each other for
+   * their whole duration with maint_mu, taken before mu and never under it. */
+  std::mutex maint_mu;
+  std::atomic<uint64_t> store_epoch{0};
+  uint64_t rc_bounce_bytes = 0, rc_piece_bytes = 0; /* GRA_RECLAIM_BOUNCE /
+                                                       _PIECE override */
+  DevBuf<uint8_t> rc_bounce; /* grow-only, allocated at the first reclaim
+                                that bounces; guarded by mu */
+  DevBuf<RcTask> rc_tasks;
 
   int init(const GraEngineOpts &o);
   ~GraEngine();
@@ -856,6 +882,13 @@ int GraEngine::init(const GraEngineOpts &o) {
     long v = atol(g);
     copy_grid = (uint32_t)(v < 1 ? 1 : v > 2048 ? 2048 : v);
   }
+  /* gra_reclaim's sizes; the overrides are for tests */
+  rc_bounce_bytes = 64ull << 20;
+  rc_piece_bytes = 16u << 20;
+  if (const char *g = getenv("GRA_RECLAIM_BOUNCE"))
+    rc_bounce_bytes = strtoull(g, nullptr, 10);
+  if (const char *g = getenv("GRA_RECLAIM_PIECE"))
+    rc_piece_bytes = strtoull(g, nullptr, 10);
   group_cap = opts.nshards + 1 > 65536 ? opts.nshards + 1 : 65536;
   (void)hipGetLastError(); /* consume any sticky per-thread error a prior
                               (possibly intentionally failing) call left —
@@ -1875,18 +1908,42 @@ static int fetch_run_impl(GraEngine *e, Run &r) {
   return GRA_OK;
 }
 
+/* The lazy fetch of gra_get and of gra_scan's host path: re-snapshot the
+ * shard's run list and fetch every run that has no host copy yet, with the
+ * engine mutex held around the shard's. With e->mu held no gra_reclaim is
+ * moving the arena, and the offsets of LISTED runs read under ss.mu are then
+ * current (a snapshot taken earlier may hold runs a compaction has unlisted
+ * and a reclaim has overwritten since). Fetched copies are run-relative and
+ * stay valid wherever the device bytes go later. */
+static int fetch_listed_runs(GraEngine *e, ShardState &ss,
+                             std::vector<std::shared_ptr<Run>> *runs,
+                             bool skip_empty) {
+  std::lock_guard<std::mutex> lk_engine(e->mu);
+  std::lock_guard<std::mutex> lk(ss.mu);
+  runs->clear();
+  for (const auto &rp : ss.runs) {
+    if (skip_empty && rp->n_entries == 0) continue;
+    int rc = fetch_run_impl(e, *rp);
+    if (rc != GRA_OK) return rc;
+    runs->push_back(rp);
+  }
+  return GRA_OK;
+}
+
 int gra_get(GraDb *db, const void *key, size_t klen, void *buf, size_t cap,
             size_t *vlen) {
   GraEngine *e = db->e;
   ShardState &ss = e->shards[db->shard];
   std::vector<std::shared_ptr<Run>> runs;
+  bool all_resident = true;
   {
     std::lock_guard<std::mutex> lk(ss.mu);
     runs = ss.runs;
-    for (auto &r : runs) { /* lazy fetch under the shard lock */
-      int rc = fetch_run_impl(e, *r);
-      if (rc != GRA_OK) return rc;
-    }
+    for (auto &r : runs) all_resident = all_resident && r->resident();
+  }
+  if (!all_resident) {
+    int rc = fetch_listed_runs(e, ss, &runs, false);
+    if (rc != GRA_OK) return rc;
   }
   std::string out;
   int rc = run_get(runs, key, klen, e->opts.merge_op, &out);
@@ -1924,37 +1981,46 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
    * call to the host path */
   std::vector<RunView> views;
   std::vector<std::shared_ptr<Run>> host_runs, unbuilt;
-  {
-    std::lock_guard<std::mutex> lk(ss.mu);
-    views.reserve(ss.runs.size());
-    for (auto it = ss.runs.rbegin(); it != ss.runs.rend(); ++it) {
-      const Run &r = **it;
-      if (r.n_entries == 0) continue;
-      if (r.hdr_cur == UINT64_MAX) {
-        host_runs.push_back(*it); /* oldest..newest order irrelevant: probe
-                                     tracks max seqs */
-      } else {
-        views.push_back(view_of(r));
-        if (!r.kpref_built) unbuilt.push_back(*it); /* racy pre-filter:
-                                     re-checked under e->mu (rebuilds are
-                                     idempotent anyway) */
-      }
-    }
-  }
-  if (views.empty()) {
-    if (host_runs.empty()) {
-      for (uint32_t q = 0; q < nq; q++) {
-        out[q].status = GRA_GET_MISS;
-        out[q].vlen = 0;
-      }
-    } else { /* purely host-resident shard: answer via the host path */
-      for (uint32_t q = 0; q < nq; q++) out[q].status = GRA_GET_NEEDS_HOST;
-    }
-    return GRA_OK;
-  }
   /* grow-only device staging cached on the engine (serialized with other
    * engine ops by mu; a serving deployment would shard this per stream) */
-  std::lock_guard<std::mutex> lk_engine(e->mu);
+  std::unique_lock<std::mutex> lk_engine(e->mu, std::defer_lock);
+  for (;;) { /* once, unless a gra_reclaim ran under the snapshot */
+    const uint64_t epoch = e->store_epoch.load(std::memory_order_acquire);
+    views.clear();
+    host_runs.clear();
+    unbuilt.clear();
+    {
+      std::lock_guard<std::mutex> lk(ss.mu);
+      views.reserve(ss.runs.size());
+      for (auto it = ss.runs.rbegin(); it != ss.runs.rend(); ++it) {
+        const Run &r = **it;
+        if (r.n_entries == 0) continue;
+        if (r.hdr_cur == UINT64_MAX) {
+          host_runs.push_back(*it); /* oldest..newest order irrelevant: probe
+                                       tracks max seqs */
+        } else {
+          views.push_back(view_of(r));
+          if (!r.kpref_built) unbuilt.push_back(*it); /* racy pre-filter:
+                                       re-checked under e->mu (rebuilds are
+                                       idempotent anyway) */
+        }
+      }
+    }
+    if (views.empty()) {
+      if (host_runs.empty()) {
+        for (uint32_t q = 0; q < nq; q++) {
+          out[q].status = GRA_GET_MISS;
+          out[q].vlen = 0;
+        }
+      } else { /* purely host-resident shard: answer via the host path */
+        for (uint32_t q = 0; q < nq; q++) out[q].status = GRA_GET_NEEDS_HOST;
+      }
+      return GRA_OK;
+    }
+    lk_engine.lock();
+    if (e->store_epoch.load(std::memory_order_acquire) == epoch) break;
+    lk_engine.unlock(); /* the offsets are stale (GraEngine::store_epoch) */
+  }
   size_t vb = (size_t)nq * val_stride;
   auto &mg = e->mg;
   const bool mixed = !host_runs.empty();
@@ -2157,7 +2223,10 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
 
 /* ---- gra_scan: ordered range scan (≅ ApplicationDB::NewIterator) ---- */
 
-enum { kScanTakeHostPath = 100 }; /* scan_device: not servable on device */
+enum {
+  kScanTakeHostPath = 100, /* scan_device: not servable on device */
+  kScanStale = 101, /* scan_device: a gra_reclaim ran under the snapshot */
+};
 
 /* The scan chain's front end, shared by gra_scan and gra_compact (both run
  * it under e->mu on the shared ScCache): collect -> bitonic sort -> with a
@@ -2230,17 +2299,20 @@ static bool sc_launch_front(GraEngine *e, const std::vector<RunView> &views,
   return true;
 }
 
-/* Device path over a snapshot of device-resident runs. One sync to learn
- * the page size, then the result copy. Returns GRA_OK / GRA_BUF_TOO_SMALL /
- * GRA_ERR, or kScanTakeHostPath when the tombstone list overflows or staging
- * cannot be allocated. */
+/* Device path over a snapshot of device-resident runs, taken after
+ * store_epoch read `epoch`. One sync to learn the page size, then the result
+ * copy. Returns GRA_OK / GRA_BUF_TOO_SMALL / GRA_ERR, kScanTakeHostPath when
+ * the tombstone list overflows or staging cannot be allocated, or kScanStale
+ * (nothing launched) when the epoch has moved: the caller snapshots again. */
 static int scan_device(GraEngine *e, const std::vector<RunView> &views,
                        bool sorted0, uint64_t total_payload, const uint8_t *lo,
                        uint32_t lo_len, const uint8_t *hi,
                        uint32_t hi_len, bool has_hi, uint32_t max_entries,
                        GraScanEntry *out, uint8_t *buf, size_t cap,
-                       GraScanInfo *info) {
+                       GraScanInfo *info, uint64_t epoch) {
   std::lock_guard<std::mutex> lk_engine(e->mu);
+  if (e->store_epoch.load(std::memory_order_acquire) != epoch)
+    return kScanStale;
   auto &sc = e->sc;
   /* 0 = off (the default chain, kernel for kernel), 1 = concat, 2 = u64add */
   const int fold = !e->opts.fold_on_device              ? 0
@@ -2379,50 +2451,59 @@ int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
     int c = m ? memcmp(lo, hi, m) : 0;
     empty_range = c > 0 || (c == 0 && lo_len >= hi_len);
   }
-  /* snapshot the run list, as gra_multiget does */
+  /* snapshot the run list, as gra_multiget does (and again if a
+   * gra_reclaim ran under the snapshot: GraEngine::store_epoch) */
   std::vector<RunView> views;
   std::vector<std::shared_ptr<Run>> runs;
-  bool any_host = false, sorted0 = false;
-  uint64_t dev_payload = 0;
-  {
-    std::lock_guard<std::mutex> lk(ss.mu);
-    for (const auto &rp : ss.runs) {
-      if (rp->n_entries == 0) continue;
-      runs.push_back(rp);
-      if (rp->hdr_cur == UINT64_MAX)
-        any_host = true;
-      else {
-        /* at most one sorted run, and it is the shard's oldest */
-        if (views.empty() && rp->sorted) sorted0 = true;
-        views.push_back(view_of(*rp));
-        dev_payload += rp->payload_bytes;
+  bool all_resident = true;
+  for (;;) {
+    const uint64_t epoch = e->store_epoch.load(std::memory_order_acquire);
+    bool any_host = false, sorted0 = false;
+    uint64_t dev_payload = 0;
+    views.clear();
+    runs.clear();
+    all_resident = true;
+    info->served_by = GRA_SCAN_DEVICE;
+    {
+      std::lock_guard<std::mutex> lk(ss.mu);
+      for (const auto &rp : ss.runs) {
+        if (rp->n_entries == 0) continue;
+        runs.push_back(rp);
+        all_resident = all_resident && rp->resident();
+        if (rp->hdr_cur == UINT64_MAX)
+          any_host = true;
+        else {
+          /* at most one sorted run, and it is the shard's oldest */
+          if (views.empty() && rp->sorted) sorted0 = true;
+          views.push_back(view_of(*rp));
+          dev_payload += rp->payload_bytes;
+        }
       }
     }
-  }
-  /* a shard whose device path would enter a sorted run says so for every
-   * range, the empty one included */
-  const bool device_ok = !any_host && views.size() <= 65535;
-  if (device_ok && sorted0) info->served_by = GRA_SCAN_DEVICE_INDEXED;
-  if (runs.empty() || empty_range) return GRA_OK;
-  if (device_ok) { /* grid.y = one row per run */
-    /* a stored key is shorter than kScMaxBound, so a longer bound orders
-     * against every key exactly as its first kScMaxBound bytes do */
+    /* a shard whose device path would enter a sorted run says so for every
+     * range, the empty one included */
+    const bool device_ok = !any_host && views.size() <= 65535;
+    if (device_ok && sorted0) info->served_by = GRA_SCAN_DEVICE_INDEXED;
+    if (runs.empty() || empty_range) return GRA_OK;
+    if (!device_ok) break;
+    /* grid.y = one row per run. A stored key is shorter than kScMaxBound, so
+     * a longer bound orders against every key exactly as its first
+     * kScMaxBound bytes do */
     uint32_t l32 = lo_len < kScMaxBound ? (uint32_t)lo_len : kScMaxBound;
     uint32_t h32 = hi_len < kScMaxBound ? (uint32_t)hi_len : kScMaxBound;
     int rc = scan_device(e, views, sorted0, dev_payload, lo, l32, hi, h32,
-                         has_hi, max_entries, out, buf, cap, info);
+                         has_hi, max_entries, out, buf, cap, info, epoch);
+    if (rc == kScanStale) continue;
     if (rc != kScanTakeHostPath) return rc;
+    break;
   }
   /* host path: host-origin runs in the shard (leader writes, drained
    * arenas), tombstone-list overflow, or no device staging */
   info->served_by = GRA_SCAN_HOST;
   info->candidates = 0;
-  {
-    std::lock_guard<std::mutex> lk(ss.mu);
-    for (auto &r : runs) { /* lazy fetch under the shard lock, as gra_get */
-      int rc = fetch_run_impl(e, *r);
-      if (rc != GRA_OK) return rc;
-    }
+  if (!all_resident) { /* lazy fetch, as gra_get */
+    int rc = fetch_listed_runs(e, ss, &runs, true);
+    if (rc != GRA_OK) return rc;
   }
   ScanResult res;
   int rc = run_scan(runs, lo, lo_len, has_hi ? hi : nullptr, hi_len,
@@ -2519,6 +2600,10 @@ int gra_compact(GraDb *db, GraCompactInfo *info) {
     return GRA_ERR;
   }
   ShardState &ss = e->shards[db->shard];
+  /* no gra_reclaim from the snapshot to the listing of the output run: the
+   * snapshot's offsets stay good and the unlisted output run, which a
+   * reclaim would not move, is never under one (GraEngine::maint_mu) */
+  std::lock_guard<std::mutex> lk_maint(e->maint_mu);
   /* the prefix: the leading device-resident runs, oldest first */
   std::vector<std::shared_ptr<Run>> snap;
   {
@@ -2590,33 +2675,237 @@ int gra_compact(GraDb *db, GraCompactInfo *info) {
   return GRA_OK;
 }
 
+/* ---- gra_store_usage / gra_reclaim: the arena's fill, and sliding the live
+ * runs down to get the dead space back ---- */
+
+/* the bump cursor, stream-ordered behind everything queued on e->stream;
+ * caller holds e->mu */
+static int read_cursor_locked(GraEngine *e, uint64_t *cur) {
+  HIP_TRY(hipMemcpyAsync(cur, e->d_cursor, 8, hipMemcpyDeviceToHost,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return GRA_OK;
+}
+
+int gra_store_usage(GraEngine *e, GraStoreUsage *out) {
+  if (!e || !out) {
+    g_err = "gra_store_usage: null argument";
+    return GRA_ERR;
+  }
+  memset(out, 0, sizeof(*out));
+  std::lock_guard<std::mutex> lk(e->mu);
+  int rc = read_cursor_locked(e, &out->used);
+  if (rc != GRA_OK) return rc;
+  out->capacity = e->opts.store_bytes;
+  for (ShardState &ss : e->shards) {
+    std::lock_guard<std::mutex> lk_shard(ss.mu);
+    for (const auto &rp : ss.runs)
+      if (rp->hdr_cur != UINT64_MAX && rp->n_entries > 0)
+        out->live += (uint64_t)rp->n_entries * sizeof(wb::RecHdr) +
+                     rp->payload_bytes;
+  }
+  return GRA_OK;
+}
+
+int gra_reclaim(GraEngine *e, GraReclaimInfo *info) {
+  if (!e || !info) {
+    g_err = "gra_reclaim: null argument";
+    return GRA_ERR;
+  }
+  memset(info, 0, sizeof(*info));
+  if (e->opts.store_ring) {
+    g_err = "gra_reclaim: a store_ring engine keeps no runs";
+    return GRA_ERR;
+  }
+  std::lock_guard<std::mutex> lk_maint(e->maint_mu);
+  std::lock_guard<std::mutex> lk(e->mu);
+  /* GRA_RECLAIM_TIMING=1: the call's phases on stderr (scripts/
+   * bench_reclaim.py sets it, to tell the copies from the host's share) */
+  static const bool timing = env_flag("GRA_RECLAIM_TIMING");
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto ms = [](std::chrono::steady_clock::time_point a,
+               std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+  };
+  const auto t_start = now();
+  /* every pending tick ingested: no kernel writes the arena, k_drain has
+   * read what it reads, and every run is listed */
+  int rc = e->flush_locked();
+  if (rc != GRA_OK) return rc;
+  uint64_t used = 0;
+  rc = read_cursor_locked(e, &used);
+  if (rc != GRA_OK) return rc;
+  /* two segments per device-resident run: refs[tag] says whose. Device runs
+   * are listed by ingest (under e->mu) and gra_compact (under maint_mu)
+   * only, so the set is fixed until this call returns; leader writes append
+   * host runs meanwhile, which are not in the arena. */
+  struct Ref {
+    std::shared_ptr<Run> run;
+    uint32_t shard;
+  };
+  std::vector<Ref> refs; /* tag / 2 */
+  std::vector<RcSegment> segs;
+  for (uint32_t s = 0; s < e->opts.nshards; s++) {
+    ShardState &ss = e->shards[s];
+    std::lock_guard<std::mutex> lk_shard(ss.mu);
+    for (const auto &rp : ss.runs) {
+      if (rp->hdr_cur == UINT64_MAX || rp->n_entries == 0) continue;
+      RcSegment h, p;
+      h.src = rp->hdr_cur;
+      h.nbytes = (uint64_t)rp->n_entries * sizeof(wb::RecHdr);
+      h.tag = 2 * refs.size();
+      p.src = rp->payload_cur;
+      p.nbytes = rp->payload_bytes; /* a truncated run's upper bound: all */
+      p.tag = h.tag + 1;
+      segs.push_back(h);
+      segs.push_back(p);
+      refs.push_back({rp, s});
+    }
+  }
+  const auto t_collected = now();
+  RcPlan plan;
+  std::string why;
+  if (plan_reclaim(segs, used, e->rc_bounce_bytes, e->rc_piece_bytes, &plan,
+                   &why) != 0) {
+    g_err = "gra_reclaim: " + why + " (store untouched)";
+    return GRA_ERR;
+  }
+  info->used_before = info->used_after = used;
+  info->status = GRA_RECLAIM_NOTHING;
+  if (plan.new_cursor >= used) return GRA_OK; /* empty or already dense */
+  /* the task list: a direct batch is one range of it, a bounce batch two
+   * (store -> buffer, buffer -> store) */
+  struct Launch {
+    size_t first;
+    uint32_t count;
+    bool from_bounce, to_bounce;
+  };
+  std::vector<RcTask> tasks;
+  std::vector<Launch> launches;
+  bool bounces = false;
+  for (const RcBatch &b : plan.batches) {
+    const RcPiece *pc = plan.pieces.data() + b.first;
+    if (b.kind == kRcDirect) {
+      launches.push_back({tasks.size(), b.count, false, false});
+      for (uint32_t i = 0; i < b.count; i++)
+        tasks.push_back({pc[i].src, pc[i].dst, pc[i].nbytes});
+    } else {
+      bounces = true;
+      launches.push_back({tasks.size(), b.count, false, true});
+      for (uint32_t i = 0; i < b.count; i++)
+        tasks.push_back({pc[i].src, pc[i].bnc, pc[i].nbytes});
+      launches.push_back({tasks.size(), b.count, true, false});
+      for (uint32_t i = 0; i < b.count; i++)
+        tasks.push_back({pc[i].bnc, pc[i].dst, pc[i].nbytes});
+    }
+  }
+  if ((!tasks.empty() &&
+       !e->rc_tasks.reserve_bytes(tasks.size() * sizeof(RcTask), true)) ||
+      (bounces && !e->rc_bounce.reserve_bytes(e->rc_bounce_bytes + 16))) {
+    g_err = "gra_reclaim: device staging allocation failed (store untouched)";
+    return GRA_ERR;
+  }
+  const auto t_planned = now();
+  /* from here on a failure leaves the arena half moved */
+  hipStream_t st = e->stream;
+  bool ok = tasks.empty() ||
+            hipMemcpyAsync(e->rc_tasks, tasks.data(),
+                           tasks.size() * sizeof(RcTask),
+                           hipMemcpyHostToDevice, st) == hipSuccess;
+  for (size_t i = 0; ok && i < launches.size(); i++) {
+    const Launch &l = launches[i];
+    /* 4 waves a block, one worker a wave; past the grid cap the waves
+     * stride over the workers */
+    const uint32_t units = rc_units(l.count, e->rc_piece_bytes);
+    uint64_t nblk = ((uint64_t)l.count * units + 3) / 4;
+    hipLaunchKernelGGL(k_rc_move,
+                       dim3(nblk < kRcGridBlocks ? (uint32_t)nblk
+                                                 : kRcGridBlocks),
+                       dim3(256), 0, st,
+                       l.from_bounce ? e->rc_bounce.get() : e->d_store,
+                       l.to_bounce ? e->rc_bounce.get() : e->d_store,
+                       e->rc_tasks + l.first, l.count, units);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  const uint64_t new_cursor = plan.new_cursor;
+  ok = ok && hipMemcpyAsync(e->d_cursor, &new_cursor, 8, hipMemcpyHostToDevice,
+                            st) == hipSuccess;
+  ok = (hipStreamSynchronize(st) == hipSuccess) && ok;
+  if (!ok) {
+    g_err = "gra_reclaim: a device copy failed after the move began — the "
+            "store arena is undefined, destroy the engine";
+    return GRA_ERR;
+  }
+  const auto t_copied = now();
+  /* the bytes are in place: point the runs at them. refs are grouped by
+   * shard, so each ss.mu is taken once */
+  std::vector<uint64_t> new_off(segs.size());
+  for (const RcSegment &s : plan.segs) new_off[s.tag] = s.dst;
+  for (size_t i = 0; i < refs.size();) {
+    ShardState &ss = e->shards[refs[i].shard];
+    std::lock_guard<std::mutex> lk_shard(ss.mu);
+    for (const uint32_t shard = refs[i].shard;
+         i < refs.size() && refs[i].shard == shard; i++) {
+      Run &r = *refs[i].run;
+      if (r.hdr_cur != new_off[2 * i] || r.payload_cur != new_off[2 * i + 1])
+        info->runs_moved++;
+      r.hdr_cur = new_off[2 * i];
+      r.payload_cur = new_off[2 * i + 1];
+    }
+  }
+  /* after the last rewrite (GraEngine::store_epoch) */
+  e->store_epoch.fetch_add(1, std::memory_order_release);
+  info->status = GRA_RECLAIM_DONE;
+  info->batches = (uint32_t)plan.batches.size();
+  info->used_after = new_cursor;
+  info->bytes_moved = plan.bytes_moved;
+  info->bytes_bounced = plan.bytes_bounced;
+  if (timing)
+    fprintf(stderr,
+            "[gra] reclaim: flush+collect %.3f ms (%zu segments), plan+alloc "
+            "%.3f ms (%zu tasks), upload+%zu launches+sync %.3f ms, rewrite "
+            "%.3f ms\n",
+            ms(t_start, t_collected), segs.size(), ms(t_collected, t_planned),
+            tasks.size(), launches.size(), ms(t_planned, t_copied),
+            ms(t_copied, now()));
+  return GRA_OK;
+}
+
 int gra_shard_checksum(GraDb *db, uint64_t *out) {
   GraEngine *e = db->e;
   ShardState &ss = e->shards[db->shard];
   std::vector<RunView> views;
   uint64_t host_sum = 0;
-  {
-    std::lock_guard<std::mutex> lk(ss.mu);
-    for (const auto &rp : ss.runs) {
-      const Run &r = *rp;
-      if (r.n_entries == 0) continue;
-      if (r.hdr_cur == UINT64_MAX) { /* host-origin/drained: fold on host */
-        const wb::RecHdr *h = (const wb::RecHdr *)r.hdrs_data();
-        const uint8_t *pay = r.payload_data();
-        for (uint32_t i = 0; i < r.n_entries; i++)
-          host_sum += rec_hash_cs(h[i].seq, h[i].type, h[i].key_len,
-                                  h[i].val_len, pay + h[i].kv_off,
-                                  pay + h[i].kv_off + h[i].key_len);
-      } else {
-        views.push_back(view_of(r));
+  std::unique_lock<std::mutex> lk(e->mu, std::defer_lock);
+  for (;;) { /* once, unless a gra_reclaim ran under the snapshot */
+    const uint64_t epoch = e->store_epoch.load(std::memory_order_acquire);
+    views.clear();
+    host_sum = 0;
+    {
+      std::lock_guard<std::mutex> lk_shard(ss.mu);
+      for (const auto &rp : ss.runs) {
+        const Run &r = *rp;
+        if (r.n_entries == 0) continue;
+        if (r.hdr_cur == UINT64_MAX) { /* host-origin/drained: fold on host */
+          const wb::RecHdr *h = (const wb::RecHdr *)r.hdrs_data();
+          const uint8_t *pay = r.payload_data();
+          for (uint32_t i = 0; i < r.n_entries; i++)
+            host_sum += rec_hash_cs(h[i].seq, h[i].type, h[i].key_len,
+                                    h[i].val_len, pay + h[i].kv_off,
+                                    pay + h[i].kv_off + h[i].key_len);
+        } else {
+          views.push_back(view_of(r));
+        }
       }
     }
+    if (views.empty()) {
+      *out = host_sum;
+      return GRA_OK;
+    }
+    lk.lock();
+    if (e->store_epoch.load(std::memory_order_acquire) == epoch) break;
+    lk.unlock(); /* the offsets are stale (GraEngine::store_epoch) */
   }
-  if (views.empty()) {
-    *out = host_sum;
-    return GRA_OK;
-  }
-  std::lock_guard<std::mutex> lk(e->mu);
   DevBuf<RunView> d_runs; /* per call: freed on every return */
   DevBuf<unsigned long long> d_sum;
   uint32_t nb = views.size() < 1024 ? (uint32_t)views.size() : 1024;

@@ -393,4 +393,86 @@ bool host_build_run(const uint8_t *rep, size_t len, uint64_t base_seq, Run *out)
   return true;
 }
 
+int plan_reclaim(const std::vector<RcSegment> &segments, uint64_t used,
+                 uint64_t bounce_bytes, uint64_t piece_bytes, RcPlan *plan,
+                 std::string *err) {
+  *plan = RcPlan();
+  auto fail = [&](const char *msg) {
+    if (err) *err = msg;
+    *plan = RcPlan();
+    return 1;
+  };
+  if (piece_bytes == 0 || piece_bytes % 16 != 0 || piece_bytes > 0xFFFFFFF0ull)
+    return fail("piece size must be a positive multiple of 16 below 4 GiB");
+  if (bounce_bytes < piece_bytes)
+    return fail("bounce buffer smaller than one piece");
+  std::vector<RcSegment> &segs = plan->segs;
+  segs = segments;
+  std::sort(segs.begin(), segs.end(), [](const RcSegment &a, const RcSegment &b) {
+    return a.src != b.src ? a.src < b.src : a.nbytes < b.nbytes;
+  });
+  uint64_t src_end = 0; /* end of the segments seen so far */
+  for (const RcSegment &s : segs) {
+    if (s.src % 8 != 0 || s.nbytes % 8 != 0)
+      return fail("segment not 8-byte aligned");
+    if (s.nbytes > used || s.src > used - s.nbytes)
+      return fail("segment reaches past the cursor");
+    if (s.src < src_end) return fail("segments overlap");
+    src_end = s.src + s.nbytes;
+  }
+  /* destinations */
+  uint64_t running = 0;
+  for (RcSegment &s : segs) {
+    uint64_t dst = (running & ~15ull) | (s.src & 15);
+    if (dst < running) dst += 16;
+    s.dst = dst;
+    running = dst + s.nbytes;
+  }
+  plan->new_cursor = (running + 15) & ~15ull;
+  /* pieces of the moved segments */
+  for (size_t i = 0; i < segs.size(); i++) {
+    const RcSegment &s = segs[i];
+    if (s.dst == s.src || s.nbytes == 0) continue;
+    plan->bytes_moved += s.nbytes;
+    for (uint64_t done = 0; done < s.nbytes;) {
+      /* the first piece of a segment at 8 mod 16 stops at a 16-B boundary */
+      uint64_t room = piece_bytes - ((s.src + done) & 15);
+      uint64_t n = s.nbytes - done < room ? s.nbytes - done : room;
+      plan->pieces.push_back(
+          {s.src + done, s.dst + done, 0, (uint32_t)n, (uint32_t)i});
+      done += n;
+    }
+  }
+  /* batches */
+  std::vector<RcPiece> &pc = plan->pieces;
+  for (size_t i = 0; i < pc.size();) {
+    RcBatch b = {};
+    b.first = (uint32_t)i;
+    if (pc[i].src - pc[i].dst >= piece_bytes) {
+      b.kind = kRcDirect;
+      const uint64_t src_begin = pc[i].src;
+      while (i < pc.size() && pc[i].dst + pc[i].nbytes <= src_begin) {
+        b.bytes += pc[i].nbytes;
+        i++;
+      }
+    } else {
+      b.kind = kRcBounce;
+      uint64_t fill = 0; /* bytes of the bounce buffer taken */
+      /* until the buffer is full or the gap has grown to hold a piece */
+      while (i < pc.size() && pc[i].src - pc[i].dst < piece_bytes) {
+        uint64_t bnc = ((fill + 15) & ~15ull) + (pc[i].src & 15);
+        if (bnc + pc[i].nbytes > bounce_bytes) break;
+        pc[i].bnc = bnc;
+        fill = bnc + pc[i].nbytes;
+        b.bytes += pc[i].nbytes;
+        i++;
+      }
+      plan->bytes_bounced += b.bytes;
+    }
+    b.count = (uint32_t)i - b.first;
+    plan->batches.push_back(b);
+  }
+  return 0;
+}
+
 } /* namespace gra */

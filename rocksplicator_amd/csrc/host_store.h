@@ -138,6 +138,62 @@ int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo,
 int run_compact(const std::vector<std::shared_ptr<Run>> &runs, int merge_op,
                 Run *out);
 
+/* The plan of gra_reclaim: where every live segment of the store arena goes
+ * when the arena is slid down, and in which copies. Plain host code, so a CPU
+ * test can hold every decision to account; the engine runs exactly this plan.
+ *
+ * A segment is a byte range [src, src + nbytes) of the arena that some
+ * device-resident run owns (its header array or its payload); src and nbytes
+ * are multiples of 8. The segments are sorted by src and walked with a running
+ * offset that starts at 0: dst is the smallest offset >= running with
+ * dst == src (mod 16), so dst <= src by induction, every 16-B chunk of the
+ * source is a 16-B chunk of the destination, and no reader meets an alignment
+ * it did not meet before. A segment with dst == src is not moved; once one
+ * moves, every later one does, and the gap src - dst never shrinks along the
+ * walk. new_cursor is the end of the last segment rounded up to 16.
+ *
+ * Moved segments are cut into pieces of at most piece_bytes (a multiple of
+ * 16; a piece of a segment at 8 mod 16 ends on a 16-B boundary, so only a
+ * segment's first piece has an 8-B head). Consecutive pieces form batches:
+ *  - kRcDirect: dst_end(batch) <= src_begin(batch), so no load of the batch
+ *    can see a store of the batch (later sources lie higher, earlier batches
+ *    are ordered before it). Taken whenever the gap at the batch's first
+ *    piece is at least piece_bytes;
+ *  - kRcBounce: otherwise. The pieces go store -> bounce buffer, then bounce
+ *    buffer -> store; RcPiece::bnc is the piece's place in the buffer
+ *    (bnc == src (mod 16)), and a batch ends before bounce_bytes.
+ * Returns 0, or 1 with *err set (plan untouched apart from being cleared)
+ * when two segments overlap, one reaches past `used`, a src or nbytes is not
+ * a multiple of 8, piece_bytes is 0 or not a multiple of 16, or bounce_bytes
+ * is smaller than piece_bytes. */
+enum : uint32_t { kRcDirect = 0, kRcBounce = 1 };
+struct RcSegment {
+  uint64_t src = 0, nbytes = 0;
+  uint64_t dst = 0;  /* filled by plan_reclaim */
+  uint64_t tag = 0;  /* the caller's: carried through the sort */
+};
+struct RcPiece {
+  uint64_t src, dst, bnc; /* bnc: bounce batches only, else 0 */
+  uint32_t nbytes;
+  uint32_t seg; /* index into RcPlan::segs */
+};
+struct RcBatch {
+  uint32_t kind;  /* kRcDirect / kRcBounce */
+  uint32_t first, count; /* pieces */
+  uint32_t _pad;
+  uint64_t bytes; /* sum of the pieces' nbytes */
+};
+struct RcPlan {
+  std::vector<RcSegment> segs; /* sorted by src, dst filled */
+  std::vector<RcPiece> pieces; /* of the moved segments, in source order */
+  std::vector<RcBatch> batches;
+  uint64_t new_cursor = 0;
+  uint64_t bytes_moved = 0, bytes_bounced = 0;
+};
+int plan_reclaim(const std::vector<RcSegment> &segments, uint64_t used,
+                 uint64_t bounce_bytes, uint64_t piece_bytes, RcPlan *plan,
+                 std::string *err);
+
 /* Host apply of one rep blob (leader write path): decodes with wb::walk and
  * builds a Run in the same format the GPU emits. Returns false on corrupt
  * rep. base_seq = first seq to assign. */

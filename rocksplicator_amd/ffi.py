@@ -77,6 +77,31 @@ class GraCompactInfo(C.Structure):
     ]
 
 
+GRA_RECLAIM_DONE = 0
+GRA_RECLAIM_NOTHING = 1
+
+
+class GraStoreUsage(C.Structure):
+    _fields_ = [
+        ("capacity", C.c_uint64),
+        ("used", C.c_uint64),
+        ("live", C.c_uint64),
+    ]
+
+
+class GraReclaimInfo(C.Structure):
+    _fields_ = [
+        ("status", C.c_uint32),
+        ("runs_moved", C.c_uint32),
+        ("batches", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("used_before", C.c_uint64),
+        ("used_after", C.c_uint64),
+        ("bytes_moved", C.c_uint64),
+        ("bytes_bounced", C.c_uint64),
+    ]
+
+
 class GraScanEntry(C.Structure):
     _fields_ = [
         ("key_off", C.c_uint32),
@@ -191,6 +216,8 @@ def load():
                              C.c_size_t, C.c_uint32, C.POINTER(GraScanEntry),
                              C.c_char_p, C.c_size_t, C.POINTER(GraScanInfo)]
     lib.gra_compact.argtypes = [C.c_void_p, C.POINTER(GraCompactInfo)]
+    lib.gra_store_usage.argtypes = [C.c_void_p, C.POINTER(GraStoreUsage)]
+    lib.gra_reclaim.argtypes = [C.c_void_p, C.POINTER(GraReclaimInfo)]
     lib.gra_shard_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.gra_pin_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8))]
     lib.gra_pin_free.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
@@ -358,6 +385,30 @@ class Engine:
         rc = self.lib.gra_flush(self.h)
         if rc != GRA_OK:
             raise RuntimeError(f"gra_flush rc={rc}: {last_error(self.lib)}")
+
+    def store_usage(self):
+        """gra_store_usage: the GraStoreUsage of the device run arena
+        (capacity, used = the bump cursor, live = bytes of the listed device
+        runs). Does not flush."""
+        u = GraStoreUsage()
+        rc = self.lib.gra_store_usage(self.h, C.byref(u))
+        if rc != GRA_OK:
+            raise RuntimeError(
+                f"gra_store_usage rc={rc}: {last_error(self.lib)}")
+        return u
+
+    def reclaim(self):
+        """gra_reclaim: flush, slide every live device run down to the bottom
+        of the arena and reset the bump cursor, so ticks and compactions get
+        the dead space back. Returns the GraReclaimInfo; info.status is
+        GRA_RECLAIM_DONE or _NOTHING. Raises RuntimeError on a store_ring
+        engine (store untouched) and when a device copy fails mid-way (the
+        engine must then be closed)."""
+        info = GraReclaimInfo()
+        rc = self.lib.gra_reclaim(self.h, C.byref(info))
+        if rc != GRA_OK:
+            raise RuntimeError(f"gra_reclaim rc={rc}: {last_error(self.lib)}")
+        return info
 
     def stats(self):
         s = GraStats()

@@ -132,6 +132,13 @@ class Replicator:
         self.engine.flush()
         return rs.db.compact()
 
+    # The arena side of compaction: slide the engine's live device runs down
+    # and hand the space of replaced runs back to the apply path. Engine-wide
+    # (one arena serves every db) and stop-the-world; operators call it with
+    # compact_db at a high-water mark of engine.store_usage().
+    def reclaim_store(self):
+        return self.engine.reclaim()
+
     # ≅ RocksDBReplicator::write -> ReplicatedDB::Write
     # (replicated_db.cpp:103-166)
     def write(self, name, rep_bytes, mode=0):

@@ -1,0 +1,518 @@
+"""gra_reclaim — the store arena's live runs slid down, the bump cursor reset
+— and gra_store_usage, against the CPU oracle. Expected values never come
+from the code under test: reads are compared with orc_get, checksums with
+orc_shard_checksum, and every byte figure (the cursor before, the bounds on
+the cursor after, the live bytes) is computed here from the parsed batches,
+as stored_bytes() in tests/test_gpu_compact.py does."""
+import pytest
+
+import fold_model as fm
+import oracle_ffi
+import rocksplicator_amd as ra
+import scan_streams as ss
+from pywb import PyBatch
+
+pytestmark = pytest.mark.gpu
+
+CAP = 1 << 20
+VCAP = 1 << 14  # oracle / get value buffer: every value here is far smaller
+NSH = 4
+FOUND, MISS, NEEDS_HOST = (ra.ffi.GRA_GET_FOUND, ra.ffi.GRA_GET_MISS,
+                           ra.ffi.GRA_GET_NEEDS_HOST)
+
+
+@pytest.fixture(scope="module")
+def olib():
+    return oracle_ffi.load()
+
+
+@pytest.fixture(scope="module")
+def streams():
+    """One scan_streams stream per shard (the compact tests' generator,
+    another seed each), 40 batches of 50 records."""
+    return [ss.make_stream(seed=21 + s, n_records=2000, n_batches=40)
+            for s in range(NSH)]
+
+
+def small_copies(monkeypatch):
+    """Every path of the copy at these sizes: pieces of 1 KiB, a 4 KiB
+    bounce buffer. Read at engine creation."""
+    monkeypatch.setenv("GRA_RECLAIM_BOUNCE", "4096")
+    monkeypatch.setenv("GRA_RECLAIM_PIECE", "1024")
+
+
+def pad16(n):
+    return (n + 15) & ~15
+
+
+class Layout:
+    """The test's own account of the arena: what the apply path and
+    gra_compact take from the bump cursor, and which runs are left."""
+
+    def __init__(self):
+        self.cursor = 0
+        self.runs = []  # dict(shard, n, pay, hdr_off)
+
+    def tick(self, per_shard):
+        """One tick: a header array for all shards' records (shard order),
+        padded to 16 B, then every record's key + value padded to 16 B."""
+        shape = []
+        for s in sorted(per_shard):
+            recs = [r for rep in per_shard[s] for r in fm.parse_rep(rep)]
+            if recs:
+                shape.append((s, len(recs),
+                              sum(pad16(len(k) + len(v)) for _, k, v in recs)))
+        off = self.cursor
+        for s, n, pay in shape:
+            self.runs.append(dict(shard=s, n=n, pay=pay, hdr_off=off))
+            off += 24 * n
+        self.cursor += pad16(24 * sum(n for _, n, _ in shape)) + \
+            sum(pay for _, _, pay in shape)
+
+    def compact(self, shard, live):
+        """The shard's runs replaced by one Put per live (key, value)."""
+        self.runs = [r for r in self.runs if r["shard"] != shard]
+        pay = sum(pad16(len(k) + len(v)) for k, v in live)
+        if live:
+            self.runs.append(dict(shard=shard, n=len(live), pay=pay,
+                                  hdr_off=self.cursor))
+        self.cursor += pad16(24 * len(live)) + pay
+
+    @property
+    def live_lo(self):
+        return sum(24 * r["n"] + r["pay"] for r in self.runs)
+
+    @property
+    def segments(self):
+        return 2 * len(self.runs)
+
+    def after_reclaim(self, used_after):
+        """The bound the issue sets on the cursor after a reclaim."""
+        assert self.live_lo <= used_after <= self.live_lo + 16 * self.segments
+        self.cursor = used_after
+
+
+def submit_tick(e, dbs, ost, lay, per_shard):
+    for s, reps in per_shard.items():
+        for rep in reps:
+            assert dbs[s].handle_replicate_response(rep)
+            assert ost.apply(s, rep)
+    e.flush()
+    lay.tick(per_shard)
+
+
+def oracle_values(ost, s, keys):
+    return {k: ost.get(s, k, VCAP) for k in keys}
+
+
+def live_pairs(ost, s, universe):
+    vals = oracle_values(ost, s, universe)
+    return [(k, vals[k]) for k in universe if vals[k] is not None]
+
+
+def absent_keys(universe):
+    out = [b"no-such-key-%02d" % i for i in range(10)]
+    out += [ss.cfkey(ss.CF, b"nokey%d" % i) for i in range(3)]
+    assert not set(out) & set(universe)
+    return out
+
+
+def check_reads(db, ost, s, universe, ranges, indexed=None):
+    """get, multiget_raw and scans of one shard against the oracle. A
+    NEEDS_HOST verdict (an unfolded merge chain, a mixed shard) is the
+    device declining, not an answer: get has answered that key."""
+    keys = universe + absent_keys(universe)
+    vals = oracle_values(ost, s, keys)
+    for k in keys:
+        assert db.get(k, VCAP) == vals[k], (s, k)
+    answered = 0
+    for k, (st, _, val) in zip(keys, db.multiget_raw(keys)):
+        if st == FOUND:
+            assert val == vals[k], (s, k)
+        elif st == MISS:
+            assert vals[k] is None, (s, k)
+        else:
+            assert st == NEEDS_HOST
+        answered += st != NEEDS_HOST
+    if indexed:  # a compacted device shard has nothing left to fold
+        assert answered == len(keys)
+    nonempty = 0
+    for lo, hi in ranges:
+        ents, info = db.scan_page(lo, hi, max_entries=1 << 16, cap=CAP)
+        assert info.more == 0
+        if indexed is not None:
+            want_by = (ra.GRA_SCAN_DEVICE_INDEXED if indexed
+                       else ra.GRA_SCAN_DEVICE)
+            assert info.served_by == want_by, (s, lo, hi)
+        assert ents == [(k, vals[k]) for k in universe
+                        if ss.in_range(k, lo, hi) and vals[k] is not None], \
+            (s, lo, hi)
+        nonempty += bool(ents)
+    assert nonempty >= len(ranges) // 4
+    assert db.latest_seq() == ost.latest_seq(s)
+
+
+def build_fragmented(monkeypatch, olib, streams, merge_op=1):
+    """4 shards, a one-record tick in front, then the streams flushed every
+    10 batches with an odd record count ahead of shards 1 and 3 in every
+    other tick; shards 0 and 2 compacted. -> state dict"""
+    small_copies(monkeypatch)
+    e = ra.Engine(nshards=NSH, merge_op=merge_op, fold_on_device=1,
+                  store_bytes=8 << 20, staging_bytes=16 << 20)
+    dbs = [e.open(s) for s in range(NSH)]
+    ost = oracle_ffi.Store(olib, NSH, merge_op=merge_op)
+    lay = Layout()
+    universes = [list(st[1]) for st in streams]
+    # one header in front of shard 1's: its array starts at 24 = 8 mod 16,
+    # and the hole shard 0's record leaves is smaller than any piece
+    pre = {0: [PyBatch().put(b"pre-0", b"p" * 9).data()],
+           1: [PyBatch().put(b"pre-1", b"q" * 300).put(b"pre-1b", b"r").data()],
+           3: [PyBatch().put(b"pre-3", b"s" * 40).data()]}
+    submit_tick(e, dbs, ost, lay, pre)
+    for s, k in ((0, b"pre-0"), (1, b"pre-1"), (1, b"pre-1b"), (3, b"pre-3")):
+        universes[s] = sorted(set(universes[s]) | {k})
+    for t in range(4):
+        per = {s: list(streams[s][0][10 * t:10 * t + 10]) for s in range(NSH)}
+        if t % 2:  # 501 records ahead of shards 1 and 3
+            for s in (0, 2):
+                k = b"odd-%d-%d" % (s, t)
+                per[s].append(PyBatch().put(k, b"o" * (5 + t)).data())
+                universes[s] = sorted(set(universes[s]) | {k})
+        submit_tick(e, dbs, ost, lay, per)
+    assert any(r["hdr_off"] % 16 == 8 for r in lay.runs if r["shard"] in (1, 3))
+    sums = [db.checksum() for db in dbs]
+    for s in range(NSH):  # nothing compacted yet: the oracle's record sums
+        assert sums[s] == olib.orc_shard_checksum(ost.h, s), s
+    for s in (0, 2):
+        live = live_pairs(ost, s, universes[s])
+        info = dbs[s].compact()
+        assert info.status == ra.GRA_COMPACT_DONE
+        assert info.entries_out == len(live) > 50
+        lay.compact(s, live)
+    return dict(e=e, dbs=dbs, ost=ost, lay=lay, universes=universes)
+
+
+# 1 ------------------------------------------------- moved bytes read the same
+
+def test_moved_bytes_read_the_same(monkeypatch, olib, streams):
+    st = build_fragmented(monkeypatch, olib, streams)
+    e, dbs, ost, lay = st["e"], st["dbs"], st["ost"], st["lay"]
+    sums = [db.checksum() for db in dbs]
+    for s in (1, 3):
+        assert sums[s] == olib.orc_shard_checksum(ost.h, s), s
+    usage = e.store_usage()
+    print("usage before:", usage.capacity, usage.used, usage.live,
+          "test's own:", lay.cursor, lay.live_lo)
+    assert usage.capacity == 8 << 20
+    assert usage.used == lay.cursor and usage.live == lay.live_lo
+    info = e.reclaim()
+    print("reclaim:", info.status, info.runs_moved, info.batches,
+          info.used_before, info.used_after, info.bytes_moved,
+          info.bytes_bounced)
+    assert info.status == ra.GRA_RECLAIM_DONE
+    assert info.used_after < info.used_before == lay.cursor
+    lay.after_reclaim(info.used_after)
+    assert info.bytes_bounced > 0 and info.bytes_moved > info.bytes_bounced
+    assert info.bytes_moved <= lay.live_lo
+    assert 0 < info.runs_moved <= len(lay.runs) and info.batches >= 2
+    usage = e.store_usage()
+    assert usage.used == info.used_after and usage.live == lay.live_lo
+    assert [db.checksum() for db in dbs] == sums
+    for s in range(NSH):
+        u = st["universes"][s]
+        check_reads(dbs[s], ost, s, u, ss.scan_set(6, u), indexed=s in (0, 2))
+    again = e.reclaim()
+    assert again.status == ra.GRA_RECLAIM_NOTHING
+    assert again.bytes_moved == 0 and again.bytes_bounced == 0
+    assert again.runs_moved == 0 and again.batches == 0
+    assert again.used_before == again.used_after == info.used_after
+    assert [db.checksum() for db in dbs] == sums
+    e.close()
+
+
+# 2 ------------------------------------------------------------ life goes on
+
+def test_life_goes_on_after_a_reclaim(monkeypatch, olib, streams):
+    st = build_fragmented(monkeypatch, olib, streams)
+    e, dbs, ost, lay = st["e"], st["dbs"], st["ost"], st["lay"]
+    universes = st["universes"]
+    ranges = [ss.scan_set(6, u)[:16] for u in universes]
+    info = e.reclaim()
+    assert info.status == ra.GRA_RECLAIM_DONE
+    lay.after_reclaim(info.used_after)
+    # new runs land on top of the moved ones, from the new cursor
+    for t in range(2):
+        per = {s: [PyBatch().put(b"late-%d-%d" % (s, t), b"L" * (30 + s))
+                   .merge(universes[s][7], b"\x07" * 8)
+                   .delete(universes[s][11]).data()]
+               + list(streams[(s + 1) % NSH][0][5 * t:5 * t + 5])
+               for s in range(NSH)}
+        for s in range(NSH):
+            new = {k for rep in per[s] for typ, k, _ in fm.parse_rep(rep)
+                   if typ != fm.RANGE_DELETE}
+            universes[s] = sorted(set(universes[s]) | new)
+        submit_tick(e, dbs, ost, lay, per)
+    assert e.store_usage().used == lay.cursor
+    for s in range(NSH):
+        check_reads(dbs[s], ost, s, universes[s], ranges[s])
+    for s in (0, 2):  # the sorted run plus the two new runs is the prefix
+        live = live_pairs(ost, s, universes[s])
+        cinfo = dbs[s].compact()
+        assert (cinfo.status, cinfo.runs_in, cinfo.runs_after) == \
+            (ra.GRA_COMPACT_DONE, 3, 1)
+        assert cinfo.entries_out == len(live)
+        lay.compact(s, live)
+    for s in range(NSH):
+        check_reads(dbs[s], ost, s, universes[s], ranges[s],
+                    indexed=s in (0, 2))
+    sums = [db.checksum() for db in dbs]
+    info = e.reclaim()
+    assert info.status == ra.GRA_RECLAIM_DONE
+    assert info.used_before == lay.cursor and info.bytes_moved > 0
+    lay.after_reclaim(info.used_after)
+    assert [db.checksum() for db in dbs] == sums
+    for s in range(NSH):
+        check_reads(dbs[s], ost, s, universes[s], ranges[s],
+                    indexed=s in (0, 2))
+    e.close()
+
+
+# 3 / 4 ------------------------------------------ more than the arena's worth
+
+NKEYS, VLEN = 64, 1024
+ROLL_KEYS = [b"key%05d" % i for i in range(NKEYS)]
+ROLL_TICK = pad16(24 * NKEYS) + NKEYS * pad16(8 + VLEN)  # arena bytes a tick
+ROLL_STORE = 2 << 20
+
+
+def roll_rep(t):
+    """Every key rewritten, the value naming the tick and the key."""
+    b = PyBatch()
+    for i, k in enumerate(ROLL_KEYS):
+        b.put(k, (b"%06d-%03d|" % (t, i)) * (VLEN // 11) + b"#" * (VLEN % 11))
+    return b.data()
+
+
+def roll_engine(olib):
+    e = ra.Engine(nshards=1, store_bytes=ROLL_STORE, staging_bytes=16 << 20)
+    return e, e.open(0), oracle_ffi.Store(olib, 1)
+
+
+def check_roll(db, ost):
+    keys = ROLL_KEYS + [b"key99999", b"absent"]
+    vals = oracle_values(ost, 0, keys)
+    assert sum(v is not None for v in vals.values()) == NKEYS
+    for k in keys:
+        assert db.get(k, VCAP) == vals[k], k
+    for k, (stt, _, val) in zip(keys, db.multiget_raw(keys)):
+        assert (stt, val) == ((FOUND, vals[k]) if vals[k] is not None
+                              else (MISS, b"")), k
+    ents, info = db.scan_page(b"", None, max_entries=1 << 10, cap=CAP)
+    assert info.more == 0
+    assert ents == [(k, vals[k]) for k in ROLL_KEYS]
+    assert db.latest_seq() == ost.latest_seq(0)
+
+
+def test_more_than_the_arenas_worth(olib):
+    """Four cycles of 20 ticks, compact, reclaim through a 2 MiB arena: 80
+    ticks of ROLL_TICK bytes each, more than 2.5 times the capacity. Without
+    the reclaim the 30th tick overflows. Default copy sizes."""
+    assert len(fm.parse_rep(roll_rep(0))) == NKEYS
+    assert all(len(v) == VLEN for _, _, v in fm.parse_rep(roll_rep(7)))
+    live_lo = 24 * NKEYS + NKEYS * pad16(8 + VLEN)
+    assert 80 * ROLL_TICK > 2.5 * ROLL_STORE
+    assert 22 * ROLL_TICK + 32 < ROLL_STORE < 31 * ROLL_TICK
+    e, db, ost = roll_engine(olib)
+    t = 0
+    applied = 0
+    for cycle in range(4):
+        for _ in range(20):
+            rep = roll_rep(t)
+            t += 1
+            assert db.handle_replicate_response(rep)
+            assert ost.apply(0, rep)
+            e.flush()
+            applied += ROLL_TICK
+        assert db.counters()["apply_failures"] == 0
+        cinfo = db.compact()
+        assert cinfo.status == ra.GRA_COMPACT_DONE
+        assert cinfo.entries_out == NKEYS
+        info = e.reclaim()
+        assert info.status == ra.GRA_RECLAIM_DONE
+        used = e.store_usage().used
+        print("cycle", cycle, "used before/after", info.used_before,
+              info.used_after, "moved", info.bytes_moved)
+        # one sorted run is left: two segments
+        assert used == info.used_after
+        assert live_lo <= used <= live_lo + 16 * 2
+        check_roll(db, ost)
+    assert applied == 80 * ROLL_TICK > 2.5 * ROLL_STORE
+    assert db.counters()["apply_failures"] == 0
+    e.close()
+
+
+def test_full_then_room(olib):
+    e, db, ost = roll_engine(olib)
+    t = 0
+    for _ in range(18):  # about 60 % of the arena
+        rep = roll_rep(t)
+        t += 1
+        assert db.handle_replicate_response(rep)
+        assert ost.apply(0, rep)
+        e.flush()
+    assert 0.55 * ROLL_STORE < 18 * ROLL_TICK < 0.65 * ROLL_STORE
+    assert db.compact().status == ra.GRA_COMPACT_DONE
+    failed = None
+    for _ in range(16):  # 12 more ticks do not fit behind the sorted run
+        rep = roll_rep(t)
+        assert db.handle_replicate_response(rep)
+        e.flush()
+        if db.counters()["apply_failures"] >= 1:
+            failed = rep
+            break
+        assert ost.apply(0, rep)
+        t += 1
+    assert failed is not None and t == 18 + 11
+    assert db.latest_seq() == ost.latest_seq(0)  # the durable boundary
+    assert not db.handle_replicate_response(failed)  # the one failure report
+    usage = e.store_usage()
+    assert usage.used == 30 * ROLL_TICK  # 29 ticks and the sorted run
+    assert usage.live == 12 * (24 * NKEYS + NKEYS * pad16(8 + VLEN))
+    info = e.reclaim()
+    assert info.status == ra.GRA_RECLAIM_DONE
+    assert info.used_before == usage.used
+    assert usage.live <= info.used_after <= usage.live + 16 * 2 * 12
+    assert db.latest_seq() == ost.latest_seq(0)
+    for _ in range(3):  # resumed from latest_seq() + 1: the batch that failed
+        rep = roll_rep(t)
+        t += 1
+        assert db.handle_replicate_response(rep)
+        assert ost.apply(0, rep)
+        e.flush()
+    assert db.counters()["apply_failures"] == 1
+    check_roll(db, ost)
+    e.close()
+
+
+# 5 -------------------------------------------------------------------- edges
+
+def test_reclaim_empty_engine():
+    e = ra.Engine(nshards=2, store_bytes=8 << 20, staging_bytes=16 << 20)
+    usage = e.store_usage()
+    assert (usage.capacity, usage.used, usage.live) == (8 << 20, 0, 0)
+    info = e.reclaim()
+    assert info.status == ra.GRA_RECLAIM_NOTHING
+    assert (info.used_before, info.used_after, info.bytes_moved,
+            info.runs_moved, info.batches) == (0, 0, 0, 0, 0)
+    e.close()
+
+
+def test_reclaim_refused_on_a_ring_store():
+    e = ra.Engine(nshards=1, store_ring=1, store_bytes=8 << 20,
+                  staging_bytes=16 << 20)
+    db = e.open(0)
+    assert db.handle_replicate_response(PyBatch().put(b"k", b"v").data())
+    e.flush()
+    with pytest.raises(RuntimeError, match="store_ring"):
+        e.reclaim()
+    e.close()
+
+
+def test_reclaim_leaves_a_leader_run_alone(monkeypatch, olib, streams):
+    small_copies(monkeypatch)
+    reps, universe, _ = streams[0]
+    e = ra.Engine(nshards=2, merge_op=1, store_bytes=8 << 20,
+                  staging_bytes=16 << 20)
+    dbs = [e.open(0), e.open(1)]
+    ost = oracle_ffi.Store(olib, 2, merge_op=1)
+    lay = Layout()
+    for t in range(2):
+        submit_tick(e, dbs, ost, lay, {0: reps[5 * t:5 * t + 5],
+                                       1: reps[20 + 5 * t:25 + 5 * t]})
+    lead = PyBatch().put(b"leader-key", b"lv").merge(b"abc", b"\x05" * 8).data()
+    dbs[0].write_leader(lead)
+    assert ost.apply(0, lead)
+    universe = sorted(set(universe) | {b"leader-key", b"abc"})
+    pre = oracle_ffi.Store(olib, 1, merge_op=1)  # the device prefix alone
+    for rep in reps[:10]:
+        assert pre.apply(0, rep)
+    cinfo = dbs[0].compact()
+    assert (cinfo.status, cinfo.runs_in, cinfo.runs_after) == \
+        (ra.GRA_COMPACT_DONE, 2, 2)
+    lay.compact(0, live_pairs(pre, 0, universe))
+    sums = [db.checksum() for db in dbs]
+    info = e.reclaim()
+    assert info.status == ra.GRA_RECLAIM_DONE and info.bytes_moved > 0
+    assert info.used_before == lay.cursor
+    lay.after_reclaim(info.used_after)
+    assert e.store_usage().live == lay.live_lo  # the host run is not counted
+    assert [db.checksum() for db in dbs] == sums
+    ranges = ss.scan_set(6, universe)[:16]
+    check_reads(dbs[0], ost, 0, universe, ranges)
+    ents, sinfo = dbs[0].scan_page(b"", None, max_entries=1 << 16, cap=CAP)
+    assert sinfo.served_by == ra.GRA_SCAN_HOST  # mixed shard, as before
+    assert dbs[0].get(b"leader-key") == b"lv"
+    check_reads(dbs[1], ost, 1, universe, ranges, indexed=False)
+    e.close()
+
+
+def test_reclaim_moves_a_truncated_run(monkeypatch, olib):
+    """A count-mismatch update truncates shard 1's run (its payload size is
+    then an upper bound); shard 0 in front of it is compacted, so the
+    truncated run and shard 2's move. tests/test_gpu_copy_shapes.py::
+    test_scan_skips_corrupt_update makes the same run."""
+    small_copies(monkeypatch)
+    nshards, per, cut = 3, 120, 47
+    key = lambda j: b"trunc-key-%04d" % j  # noqa: E731
+    good = lambda s, j: PyBatch().put(  # noqa: E731
+        key(j), bytes([s * 50 + j % 50]) * (40 + j % 9)).data()
+    ost = oracle_ffi.Store(olib, nshards)
+    e = ra.Engine(nshards=nshards, store_bytes=8 << 20, staging_bytes=16 << 20)
+    dbs = [e.open(s) for s in range(nshards)]
+    for j in range(per):
+        for s in range(nshards):
+            blob = good(s, j)
+            if s == 1 and j == cut:
+                bad = bytearray(blob)
+                bad[8] = 9  # header count != records in the batch
+                blob = bytes(bad)
+            assert dbs[s].handle_replicate_response(blob)
+            if s != 1 or j < cut:
+                assert ost.apply(s, blob)
+    # shard 0 again, so that its compaction has something to drop
+    for j in range(per):
+        blob = good(0, j)
+        assert dbs[0].handle_replicate_response(blob)
+        assert ost.apply(0, blob)
+    e.flush()
+    assert ost.latest_seq(1) == cut
+    assert dbs[1].counters()["apply_failures"] == 1
+    sums = [db.checksum() for db in dbs]
+    for s in range(nshards):
+        assert dbs[s].latest_seq() == ost.latest_seq(s), s
+        assert sums[s] == olib.orc_shard_checksum(ost.h, s), s
+    assert dbs[0].compact().status == ra.GRA_COMPACT_DONE
+    sums[0] = dbs[0].checksum()
+    info = e.reclaim()
+    assert info.status == ra.GRA_RECLAIM_DONE
+    assert info.runs_moved == 3 and info.bytes_moved > 0
+    # shard 1's payload counts whole: the records behind the bad update too
+    rec = lambda j: 24 + pad16(len(key(j)) + 40 + j % 9)  # noqa: E731
+    live_lo = sum(rec(j) for j in range(per)) * 2 + \
+        sum(rec(j) for j in range(per) if j != cut) - 24 * (per - cut - 1)
+    assert e.store_usage().live == live_lo
+    assert live_lo <= info.used_after <= live_lo + 16 * 6
+    assert [db.checksum() for db in dbs] == sums
+    keys = [key(j) for j in range(per)] + [b"trunc-key-9999"]
+    for s in range(nshards):
+        vals = oracle_values(ost, s, keys)
+        assert sum(v is not None for v in vals.values()) == \
+            (cut if s == 1 else per)
+        for k in keys:
+            assert dbs[s].get(k, VCAP) == vals[k], (s, k)
+        for k, (stt, _, val) in zip(keys, dbs[s].multiget_raw(keys)):
+            assert (stt, val) == ((FOUND, vals[k]) if vals[k] is not None
+                                  else (MISS, b"")), (s, k)
+        ents, _ = dbs[s].scan_page(b"", None, max_entries=1 << 10, cap=CAP)
+        assert ents == [(k, vals[k]) for k in keys if vals[k] is not None]
+    e.close()
