@@ -147,12 +147,12 @@ __global__ void __launch_bounds__(256) k_snappy(
 
 /* K1: decode walk fused with the first scan pass — each block decodes 256
  * updates, then block-scans (records, payload16) into exclusive partials +
- * a block sum. Errors accumulate in a 64-slot tick ring (no per-tick
- * memset; the fused scan2 kernel re-zeroes slot tick+32 ahead). */
+ * a block sum. The walk's totals stay in registers: per update the kernel
+ * writes a 16 B wb::EmitRec (what k_emit needs of a one-record update, or
+ * "nothing" / "walk again"), the 8 B partial and the 1 B ok flag. Errors
+ * accumulate in a 64-slot tick ring (no per-tick memset; the fused scan2
+ * kernel re-zeroes slot tick+32 ahead). */
 constexpr uint32_t kErrRing = 64;
-
-constexpr uint32_t kRecCache = 2; /* records cached per update by decode so
-                                     emit can skip the second blob walk */
 
 /* Exclusive scan of one (records, payload16) pair per thread over a block of
  * 256: shuffle scan inside each wave, then a 4-entry cross-wave combine.
@@ -198,10 +198,10 @@ static_assert(kDecodeWin % 16 == 0, "window is staged in 16 B chunks");
 
 __global__ void __launch_bounds__(256) k_decode(
     const uint8_t *__restrict__ blobs, const UpdDesc *__restrict__ descs,
-    uint32_t n, wb::WalkTotals *__restrict__ totals, uint32_t max_rec,
+    uint32_t n, wb::EmitRec *__restrict__ emitrecs, uint32_t max_rec,
     uint32_t *__restrict__ err_ring, uint32_t tick,
     uint2 *__restrict__ partial, uint2 *__restrict__ bsums,
-    wb::Rec *__restrict__ reccache, uint8_t *__restrict__ ok_out) {
+    uint8_t *__restrict__ ok_out) {
   __shared__ uint32_t stage[256 * (kDecodeWin + 4) / 4];
   uint32_t i = blockIdx.x * 256 + threadIdx.x;
   uint2 v = make_uint2(0, 0);
@@ -224,13 +224,13 @@ __global__ void __launch_bounds__(256) k_decode(
       }
     wb::WinSrc src = {(const uint8_t *)row, wb::win_bytes(d.len, kDecodeWin),
                       rep};
-    wb::Rec *cache = reccache + (size_t)i * kRecCache;
+    wb::Rec first = {};
     wb::WalkTotals t = wb::walk_src(src, d.len,
                                     [&](const wb::Rec &r, uint32_t idx) {
-                                      if (idx < kRecCache) cache[idx] = r;
+                                      if (idx == 0) first = r;
                                     });
     if (t.n_records > max_rec) t.ok = 0;
-    totals[i] = t;
+    emitrecs[i] = wb::emit_pack(t, first);
     ok_out[i] = (uint8_t)t.ok;
     if (!t.ok) atomicAdd(&err_ring[tick % kErrRing], 1u);
     if (t.ok) v = make_uint2(t.n_records, t.payload16);
@@ -290,20 +290,69 @@ __global__ void k_scan2(uint2 *__restrict__ bsums, uint32_t nblocks,
   }
 }
 
+/* Run descriptor of shard group g: where the group's headers and payload
+ * landed, from the scan at its first update and one past its last. It needs
+ * nothing k_emit or k_copy write, so it runs as the trailing blocks of the
+ * k_emit launch. The header count behind last_seq is read from the group's
+ * last blob (bytes 8..11), which is what the decode walk saw there. */
+__device__ __forceinline__ void run_desc(
+    uint32_t g, const uint8_t *__restrict__ blobs,
+    const GroupDesc *__restrict__ groups, const UpdDesc *__restrict__ descs,
+    const uint2 *__restrict__ partial, const uint2 *__restrict__ bsums,
+    uint32_t n, uint32_t nblocks, const TickPlace *__restrict__ place,
+    DevRunDesc *__restrict__ out) {
+  GroupDesc gd = groups[g];
+  auto scan_at = [&](uint32_t j) {
+    return j >= n ? bsums[nblocks] : add2(partial[j], bsums[j >> 8]);
+  };
+  uint2 s0 = scan_at(gd.first);
+  uint2 s1 = scan_at(gd.first + gd.n_upds);
+  DevRunDesc rd = {};
+  rd.shard = gd.shard;
+  rd.n_entries = s1.x - s0.x;
+  rd.payload_bytes = s1.y - s0.y;
+  rd.pay_rel_base = s0.y;
+  if (!place->overflow) {
+    rd.cur = place->cur;
+    rd.hdr_off = place->hdr_off + (uint64_t)s0.x * sizeof(wb::RecHdr);
+    rd.payload_off = place->payload_off + s0.y;
+    rd.base_seq = descs[gd.first].base_seq;
+    const UpdDesc last = descs[gd.first + gd.n_upds - 1];
+    const uint32_t hdr_count =
+        last.len >= wb::kHeaderBytes ? wb::fixed32_le(blobs + last.off + 8) : 0u;
+    rd.last_seq = last.base_seq + hdr_count - 1;
+  } else {
+    rd.n_entries = 0;
+  }
+  out[g] = rd;
+}
+
+/* K3: blocks [0, nb) write record headers, cf prefixes and copy tasks, one
+ * lane per update, from the 16 B wb::EmitRec k_decode left: nothing, the one
+ * packed record, or a second walk of the blob (batches of two or more
+ * records, keys past byte 255). Blocks [nb, gridDim.x) write the tick's run
+ * descriptors, one lane per shard group. */
 __global__ void k_emit(const uint8_t *__restrict__ blobs,
                        const UpdDesc *__restrict__ descs, uint32_t n,
-                       const wb::WalkTotals *__restrict__ totals,
+                       const wb::EmitRec *__restrict__ emitrecs,
                        const uint2 *__restrict__ partial,
                        const uint2 *__restrict__ bsums,
                        const TickPlace *__restrict__ place,
                        uint8_t *__restrict__ store,
-                       CopyTask *__restrict__ tasks,
-                       const wb::Rec *__restrict__ reccache) {
+                       CopyTask *__restrict__ tasks, uint32_t nb,
+                       const GroupDesc *__restrict__ groups, uint32_t ngroups,
+                       DevRunDesc *__restrict__ rundescs) {
+  if (blockIdx.x >= nb) { /* block-uniform; has its own overflow handling */
+    uint32_t g = (blockIdx.x - nb) * blockDim.x + threadIdx.x;
+    if (g < ngroups)
+      run_desc(g, blobs, groups, descs, partial, bsums, n, nb, place, rundescs);
+    return;
+  }
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (place->overflow) return;
-  wb::WalkTotals t = totals[i];
-  if (!t.ok || t.n_records == 0) return;
+  wb::EmitRec er = emitrecs[i];
+  if (er.kind == wb::kEmitNone) return;
   UpdDesc d = descs[i];
   uint2 base = add2(partial[i], bsums[i >> 8]); /* exclusive scan, inline */
   wb::RecHdr *hdrs = (wb::RecHdr *)(store + place->hdr_off);
@@ -354,9 +403,8 @@ __global__ void k_emit(const uint8_t *__restrict__ blobs,
     tasks[2 * (rec + idx) + 1] = tk;
     pay += (cf4 + r.key_len + cfv + r.val_len + 15u) & ~15u;
   };
-  if (t.n_records <= kRecCache) { /* decode cached these — no blob re-walk */
-    const wb::Rec *cache = reccache + (size_t)i * kRecCache;
-    for (uint32_t idx = 0; idx < t.n_records; idx++) emit_one(cache[idx], idx);
+  if (er.kind == wb::kEmitOne) { /* decode packed it — no blob re-walk */
+    emit_one(wb::emit_unpack(er), 0);
   } else {
     wb::walk_f(blobs + d.off, d.len, emit_one);
   }
@@ -427,40 +475,6 @@ __global__ void k_drain(const uint8_t *__restrict__ store,
   uint8_t *pdst = hostbuf + hb16;
   for (size_t b = i0; b < pay; b += stride)
     *(uint4 *)(pdst + b) = *(const uint4 *)(psrc + b);
-}
-
-__global__ void k_rundesc(const GroupDesc *__restrict__ groups, uint32_t ngroups,
-                          const UpdDesc *__restrict__ descs,
-                          const wb::WalkTotals *__restrict__ totals,
-                          const uint2 *__restrict__ partial,
-                          const uint2 *__restrict__ bsums, uint32_t n,
-                          uint32_t nblocks,
-                          const TickPlace *__restrict__ place,
-                          DevRunDesc *__restrict__ out) {
-  uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ngroups) return;
-  GroupDesc gd = groups[g];
-  auto scan_at = [&](uint32_t j) {
-    return j >= n ? bsums[nblocks] : add2(partial[j], bsums[j >> 8]);
-  };
-  uint2 s0 = scan_at(gd.first);
-  uint2 s1 = scan_at(gd.first + gd.n_upds);
-  DevRunDesc rd = {};
-  rd.shard = gd.shard;
-  rd.n_entries = s1.x - s0.x;
-  rd.payload_bytes = s1.y - s0.y;
-  rd.pay_rel_base = s0.y;
-  if (!place->overflow) {
-    rd.cur = place->cur;
-    rd.hdr_off = place->hdr_off + (uint64_t)s0.x * sizeof(wb::RecHdr);
-    rd.payload_off = place->payload_off + s0.y;
-    rd.base_seq = descs[gd.first].base_seq;
-    const UpdDesc last = descs[gd.first + gd.n_upds - 1];
-    rd.last_seq = last.base_seq + totals[gd.first + gd.n_upds - 1].hdr_count - 1;
-  } else {
-    rd.n_entries = 0;
-  }
-  out[g] = rd;
 }
 
 /* ---------------- device read serving (gra_multiget) ---------------- */
@@ -551,7 +565,8 @@ enum TickEvent {
   kEvAfterScan,   /* GRA_DETAILED_EVENTS only */
   kEvAfterEmit,
   kEvAfterCopy,
-  kEvMainEnd,     /* after k_rundesc */
+  kEvMainEnd,     /* right after kEvAfterCopy: the run descriptors are
+                     written inside the k_emit launch */
   kEvPublished,   /* copyout stream: run descriptors are on the host */
   kEventsPerTick
 };
@@ -644,15 +659,14 @@ struct GraEngine {
   uint32_t task_cap;
   uint32_t copy_grid; /* k_copy blocks; GRA_COPY_GRID overrides (tests) */
   uint32_t group_cap;        /* max contiguous shard-groups per tick */
-  /* decode scratch is shared by consecutive ticks: every kernel touching
-   * it (k_decode .. k_rundesc) runs on `stream`, so the stream orders a
-   * tick's last reader before the next tick's k_decode. Running decode on
-   * the prep stream under the previous tick's copy was measured and
-   * removed. */
-  wb::WalkTotals *d_totals = nullptr;
+  /* decode scratch (emit records, scan partials, block sums) is shared by
+   * consecutive ticks: every kernel touching it (k_decode, k_scan2, k_emit)
+   * runs on `stream`, so the stream orders a tick's last reader before the
+   * next tick's k_decode. Running decode on the prep stream under the
+   * previous tick's copy was measured and removed. */
+  wb::EmitRec *d_emitrecs = nullptr;
   uint2 *d_partial = nullptr;
   uint2 *d_bsums = nullptr;
-  wb::Rec *d_reccache = nullptr;
   CopyTask *d_tasks = nullptr;
   TickPlace *d_place = nullptr; /* kSlots entries: per-tick placement slot
                                    (the drain D2H snapshot on copyout must
@@ -915,10 +929,9 @@ int GraEngine::init(const GraEngineOpts &o) {
   HIP_TRY(hipMalloc(&d_store, opts.store_bytes + 16));
   HIP_TRY(hipMalloc(&d_cursor, 8));
   HIP_TRY(hipMemset(d_cursor, 0, 8));
-  HIP_TRY(hipMalloc(&d_totals, (size_t)max_upd * sizeof(wb::WalkTotals)));
+  HIP_TRY(hipMalloc(&d_emitrecs, (size_t)max_upd * sizeof(wb::EmitRec)));
   HIP_TRY(hipMalloc(&d_partial, (size_t)max_upd * sizeof(uint2)));
   HIP_TRY(hipMalloc(&d_bsums, ((size_t)max_upd / 256 + 2) * sizeof(uint2)));
-  HIP_TRY(hipMalloc(&d_reccache, (size_t)max_upd * 2 * sizeof(wb::Rec)));
   HIP_TRY(hipMalloc(&d_tasks, (size_t)task_cap * sizeof(CopyTask)));
   HIP_TRY(hipMalloc(&d_place, kSlots * sizeof(TickPlace)));
   HIP_TRY(hipMalloc(&d_groups, (size_t)group_cap * sizeof(GroupDesc)));
@@ -1018,9 +1031,8 @@ GraEngine::~GraEngine() {
     if (stage_used_ev[i]) (void)hipEventDestroy(stage_used_ev[i]);
     if (h2d_gate_ev[i]) (void)hipEventDestroy(h2d_gate_ev[i]);
   }
-  for (void *p : {(void *)d_totals, (void *)d_partial, (void *)d_bsums,
-                  (void *)d_reccache, (void *)d_store, (void *)d_cursor,
-                  (void *)d_tasks,
+  for (void *p : {(void *)d_emitrecs, (void *)d_partial, (void *)d_bsums,
+                  (void *)d_store, (void *)d_cursor, (void *)d_tasks,
                   (void *)d_place, (void *)d_groups, (void *)d_err_ring})
     if (p) (void)hipFree(p);
   shards.clear(); /* release run arenas before draining the pool */
@@ -1149,8 +1161,8 @@ int GraEngine::enqueue_tick(TickInput &in) {
     HIP_TRY(hipStreamWaitEvent(stream, t.ev[kEvSnappyDone], 0));
   }
   hipLaunchKernelGGL(k_decode, dim3(nb), dim3(256), 0, stream, d_blobs,
-                     d_descw, n, d_totals, opts.max_wb_records, d_err_ring,
-                     tick, d_partial, d_bsums, d_reccache, sl.d_ok);
+                     d_descw, n, d_emitrecs, opts.max_wb_records, d_err_ring,
+                     tick, d_partial, d_bsums, sl.d_ok);
   HIP_TRY(hipGetLastError());
   if (detailed) HIP_TRY(t.record(kEvAfterDecode, stream)); /* (+scan1) */
   TickPlace *place_slot = d_place + si;
@@ -1159,9 +1171,13 @@ int GraEngine::enqueue_tick(TickInput &in) {
                      task_cap, d_err_ring, tick);
   HIP_TRY(hipGetLastError());
   if (detailed) HIP_TRY(t.record(kEvAfterScan, stream)); /* (+reserve) */
-  hipLaunchKernelGGL(k_emit, dim3(nb), dim3(256), 0, stream, d_blobs, d_descw,
-                     n, d_totals, d_partial, d_bsums, place_slot, d_store,
-                     d_tasks, d_reccache);
+  /* trailing blocks: the tick's run descriptors (they depend on k_scan2
+   * alone, so they ride here instead of in a launch of their own after
+   * the copy) */
+  hipLaunchKernelGGL(k_emit, dim3(nb + (ngroups + 255) / 256), dim3(256), 0,
+                     stream, d_blobs, d_descw, n, d_emitrecs, d_partial,
+                     d_bsums, place_slot, d_store, d_tasks, nb,
+                     groups_for_kernel, ngroups, sl.d_rundescs);
   HIP_TRY(hipGetLastError());
   HIP_TRY(t.record(kEvAfterEmit, stream)); /* pre-copy */
   /* lanes per record by average update size, so a record's 16 B chunks
@@ -1188,10 +1204,6 @@ int GraEngine::enqueue_tick(TickInput &in) {
   HIP_TRY(t.record(kEvAfterCopy, stream));
   if (in.window_ev) /* this window's scratch fully consumed */
     HIP_TRY(hipEventRecord(in.window_ev, stream));
-  hipLaunchKernelGGL(k_rundesc, dim3((ngroups + 255) / 256), dim3(256), 0,
-                     stream, groups_for_kernel, ngroups, d_descw, d_totals,
-                     d_partial, d_bsums, n, nb, place_slot, sl.d_rundescs);
-  HIP_TRY(hipGetLastError());
   HIP_TRY(t.record(kEvMainEnd, stream));
   if (stage_buf >= 0) /* last reader of this staging buffer has retired */
     HIP_TRY(hipEventRecord(stage_used_ev[stage_buf], stream));
@@ -1231,7 +1243,7 @@ int GraEngine::enqueue_tick(TickInput &in) {
 
 static int fetch_run_impl(GraEngine *e, Run &r);
 
-/* A device run as k_rundesc described it. on_device = false leaves
+/* A device run as k_emit's descriptor blocks described it. on_device = false leaves
  * hdr_cur/payload_cur at their host-only default (ring + drain: the device
  * bytes recycle, so reads must route through the host arena). */
 static std::shared_ptr<Run> run_from(const DevRunDesc &rd, bool on_device) {

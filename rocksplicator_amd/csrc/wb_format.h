@@ -285,6 +285,72 @@ WB_HD WalkTotals walk(const uint8_t *rep, uint32_t len, Rec *emit, uint32_t cap)
   });
 }
 
+/* ---- what the decode walk hands the emit pass, 16 B per update ----
+ * Most updates carry one record, and for those the emit pass needs only the
+ * record's slices, tag and cf id: they are packed here and the blob is not
+ * walked again. Everything else about the walk (counts, payload sizes) has
+ * already gone into the scan by then. */
+enum EmitKind : uint8_t {
+  kEmitNone = 0, /* rejected blob, or no seq-consuming record */
+  kEmitOne = 1,  /* one record, packed in the EmitRec */
+  kEmitWalk = 2, /* walk the blob again */
+};
+
+constexpr uint8_t kEmitNoValue = 0; /* val_gap of a key-only record; a value
+                                       slice has a length varint of 1..5 B
+                                       between key and value, so a real gap
+                                       is never 0 */
+
+struct alignas(16) EmitRec { /* one 16 B store, one 16 B load */
+  uint32_t val_len;
+  uint32_t cf_id;
+  uint16_t key_len;
+  uint8_t key_off; /* from the blob's first byte */
+  uint8_t val_gap; /* val_off - (key_off + key_len), or kEmitNoValue */
+  uint8_t tag;     /* original tag */
+  uint8_t kind;    /* EmitKind */
+  uint16_t _pad;
+};
+static_assert(sizeof(EmitRec) == 16, "EmitRec must be 16 bytes");
+
+/* `first` is the walk's record 0; it is read only when t says there is
+ * exactly one. Packs iff the record's key starts within 255 B of the blob
+ * and is at most 65535 B long. */
+WB_HD EmitRec emit_pack(const WalkTotals &t, const Rec &first) {
+  EmitRec e = {0, 0, 0, 0, 0, 0, kEmitNone, 0};
+  if (!t.ok || t.n_records == 0) return e;
+  if (t.n_records != 1 || first.key_off > 255u || first.key_len > 65535u) {
+    e.kind = kEmitWalk;
+    return e;
+  }
+  e.val_len = first.val_len;
+  e.cf_id = first.cf_id;
+  e.key_len = (uint16_t)first.key_len;
+  e.key_off = (uint8_t)first.key_off;
+  e.val_gap = first.val_off
+                  ? (uint8_t)(first.val_off - (first.key_off + first.key_len))
+                  : kEmitNoValue;
+  e.tag = first.tag;
+  e.kind = kEmitOne;
+  return e;
+}
+
+/* The Rec the walk produced, for an EmitRec of kind kEmitOne. */
+WB_HD Rec emit_unpack(const EmitRec &e) {
+  Rec r;
+  r.key_off = e.key_off;
+  r.key_len = e.key_len;
+  r.val_off = e.val_gap != kEmitNoValue
+                  ? (uint32_t)e.key_off + e.key_len + e.val_gap
+                  : 0u;
+  r.val_len = e.val_len;
+  r.tag = e.tag;
+  r.consumes = 1;
+  r._pad = 0;
+  r.cf_id = e.cf_id;
+  return r;
+}
+
 /* ---- device store record header (one per applied record, 24 B) ---- */
 struct RecHdr {
   uint64_t seq;

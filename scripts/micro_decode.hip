@@ -11,10 +11,17 @@
  *                     when the blob starts mid-chunk; reads below the blob)
  *   restage/wW        a walk that leaves the window re-stages W bytes at the
  *                     new position instead of falling back to global bytes
+ *   win/w48/p1/u rec16
+ *                     the win/w48/p1/u parse writing one 16 B wb::EmitRec
+ *                     per update (wb::emit_pack, the engine's k_decode) where
+ *                     every other row writes WalkTotals + two cached Recs
  * Task mixes: 0 headline (16 B key, 1 KB value), 1 128 B values, 2 30 B
- * deletes, 3 eight records x 100 B, 4 cf-prefixed 1 KB puts.
+ * deletes, 3 eight records x 100 B, 4 cf-prefixed 1 KB puts, 5 two records
+ * x 500 B.
  * Every row checks its WalkTotals and cached Recs against the host walk_f
- * (ok=1). The block scan k_decode fuses is left out of every variant alike.
+ * (ok=1); the rec16 row checks every EmitRec against the pack of the host
+ * walk and unpacks the one-record ones back to the host's Rec. The block
+ * scan k_decode fuses is left out of every variant alike.
  * Args: [updates=819200] [mix=-1 (all)].
  * Build: hipcc --offload-arch=gfx950 -O3 scripts/micro_decode.hip -o build/micro_decode
  */
@@ -165,6 +172,42 @@ __global__ void __launch_bounds__(256) k_dec(const uint8_t *__restrict__ blobs,
   totals[i] = t;
 }
 
+/* The engine's k_decode writer: the window parse of win/wW/p1/u, totals kept
+ * in registers, one 16 B wb::EmitRec per update through the shared
+ * wb::emit_pack instead of WalkTotals + two cached Recs (80 B). */
+template <int W, int PAD>
+__global__ void __launch_bounds__(256) k_dec16(const uint8_t *__restrict__ blobs,
+                                               const Desc *__restrict__ descs,
+                                               uint32_t n,
+                                               wb::EmitRec *__restrict__ out) {
+  constexpr uint32_t kRow = (W + PAD) / 4;
+  __shared__ uint32_t stage[256 * kRow];
+  uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  Desc d = descs[i];
+  const uint8_t *rep = blobs + d.off;
+  uint32_t *row = stage + threadIdx.x * kRow;
+  const uint32_t nch = wb::win_chunks(d.len, W);
+  uint4 c[W / 16];
+#pragma unroll
+  for (uint32_t k = 0; k < W / 16; k++)
+    if (k < nch) c[k] = *(const uint4 *)(rep + 16 * k);
+#pragma unroll
+  for (uint32_t k = 0; k < W / 16; k++)
+    if (k < nch) {
+      row[4 * k + 0] = c[k].x;
+      row[4 * k + 1] = c[k].y;
+      row[4 * k + 2] = c[k].z;
+      row[4 * k + 3] = c[k].w;
+    }
+  wb::WinSrc src = {(const uint8_t *)row, wb::win_bytes(d.len, W), rep};
+  wb::Rec first = {};
+  wb::WalkTotals t = wb::walk_src(src, d.len, [&](const wb::Rec &r, uint32_t idx) {
+    if (idx == 0) first = r;
+  });
+  out[i] = wb::emit_pack(t, first);
+}
+
 /* ---- host-side blob building ---- */
 static void put_varint(std::vector<uint8_t> &b, uint32_t v) {
   while (v >= 0x80) {
@@ -203,12 +246,20 @@ static void one_blob(std::vector<uint8_t> &b, int mix, uint32_t i) {
         put_varint(b, 81); put_bytes(b, 81, i + r);
       }
       break;
-    default: /* cf-prefixed Put, 1- to 5-byte cf varint */
+    case 4: /* cf-prefixed Put, 1- to 5-byte cf varint */
       header(b, i, 1);
       b.push_back(wb::kCfValue);
       put_varint(b, 1u << (7 * (i % 5)));
       put_varint(b, 16); put_bytes(b, 16, i);
       put_varint(b, 1024); put_bytes(b, 1024, i);
+      break;
+    default: /* two records per batch, 16 B keys, 500 B values */
+      header(b, i, 2);
+      for (uint32_t r = 0; r < 2; r++) {
+        b.push_back(wb::kValue);
+        put_varint(b, 16); put_bytes(b, 16, i + r);
+        put_varint(b, 500); put_bytes(b, 500, i + r);
+      }
       break;
   }
 }
@@ -221,12 +272,13 @@ struct HostRef {
 int main(int argc, char **argv) {
   uint32_t n = argc > 1 ? atoi(argv[1]) : 819200;
   int only = argc > 2 ? atoi(argv[2]) : -1;
-  const char *mix_name[5] = {"headline 16B/1KB", "128 B values", "30 B deletes",
-                             "8 records x 100 B", "cf-prefixed 1KB"};
+  const char *mix_name[6] = {"headline 16B/1KB", "128 B values", "30 B deletes",
+                             "8 records x 100 B", "cf-prefixed 1KB",
+                             "2 records x 500 B"};
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
-  for (int mix = 0; mix < 5; mix++) {
+  for (int mix = 0; mix < 6; mix++) {
     if (only >= 0 && mix != only) continue;
     std::vector<uint8_t> arena;
     std::vector<Desc> descs(n);
@@ -248,6 +300,8 @@ int main(int argc, char **argv) {
     Desc *d_descs;
     wb::WalkTotals *d_totals;
     wb::Rec *d_cache;
+    wb::EmitRec *d_emit;
+    CHECK(hipMalloc(&d_emit, (size_t)n * sizeof(wb::EmitRec)));
     CHECK(hipMalloc(&d_blobs, arena.size() + 16));
     CHECK(hipMalloc(&d_descs, (size_t)n * sizeof(Desc)));
     CHECK(hipMalloc(&d_totals, (size_t)n * sizeof(wb::WalkTotals)));
@@ -284,11 +338,42 @@ int main(int argc, char **argv) {
       printf("%-18s ok=%d  %7.1f us/launch  %6.2f G upd/s\n", name, ok,
              ms * 1000 / 20, n * 20.0 / (ms * 1e-3) / 1e9);
     };
+    /* the 16 B writer: every EmitRec equals the pack of the host walk, and
+     * a kind-1 record unpacks to the host walk's first Rec */
+    std::vector<wb::EmitRec> got_e(n);
+    auto run16 = [&](const char *name, auto kern) {
+      CHECK(hipMemset(d_emit, 0xEE, (size_t)n * sizeof(wb::EmitRec)));
+      kern(); /* warmup + correctness */
+      CHECK(hipMemcpy(got_e.data(), d_emit, (size_t)n * sizeof(wb::EmitRec),
+                      hipMemcpyDeviceToHost));
+      bool ok = true;
+      for (uint32_t i = 0; i < n && ok; i++) {
+        wb::EmitRec want = wb::emit_pack(ref[i].t, ref[i].rec[0]);
+        ok = memcmp(&got_e[i], &want, sizeof want) == 0;
+        if (ok && got_e[i].kind == wb::kEmitOne) {
+          wb::Rec back = wb::emit_unpack(got_e[i]);
+          ok = memcmp(&back, &ref[i].rec[0], sizeof back) == 0;
+        }
+      }
+      CHECK(hipEventRecord(e0));
+      for (int i = 0; i < 20; i++) kern();
+      CHECK(hipEventRecord(e1));
+      CHECK(hipEventSynchronize(e1));
+      float ms;
+      CHECK(hipEventElapsedTime(&ms, e0, e1));
+      printf("%-18s ok=%d  %7.1f us/launch  %6.2f G upd/s\n", name, ok,
+             ms * 1000 / 20, n * 20.0 / (ms * 1e-3) / 1e9);
+    };
     dim3 grid((n + 255) / 256), blk(256);
 #define RUND(NAME, MODE, W, PAD) run(NAME, [&] { \
     hipLaunchKernelGGL((k_dec<MODE, W, PAD>), grid, blk, 0, 0, d_blobs, d_descs, n, d_totals, d_cache); })
     RUND("global", kGlobal, 16, 0);
     RUND("win/w48/p1/u", kWinUnaligned, 48, 4);
+    run16("win/w48/p1/u rec16", [&] {
+      hipLaunchKernelGGL((k_dec16<48, 4>), grid, blk, 0, 0, d_blobs, d_descs, n,
+                         d_emit);
+    });
+    RUND("win/w48/p1/u", kWinUnaligned, 48, 4); /* again, beside rec16 */
     RUND("win/w64/p1/u", kWinUnaligned, 64, 4);
     RUND("win/w128/p1/u", kWinUnaligned, 128, 4);
     RUND("win/w48/p0/u", kWinUnaligned, 48, 0);
@@ -302,6 +387,7 @@ int main(int argc, char **argv) {
     CHECK(hipFree(d_descs));
     CHECK(hipFree(d_totals));
     CHECK(hipFree(d_cache));
+    CHECK(hipFree(d_emit));
   }
   return 0;
 }
