@@ -6,16 +6,19 @@
  * ticks; each tick runs a GPU pipeline over blobs resident in HBM:
  *
  *   K1 decode   — per-update sequential walk of the WriteBatch rep (varint
- *                 record-boundary discovery, validation, totals)
- *   K2 scan     — exclusive prefix sums over (records, payload bytes)
- *   K3 reserve  — bump-reserve tick space in the device run store (stream-
- *                 ordered single-thread kernel; ring or linear)
- *   K4 emit     — second walk emits 24-B record headers (seq/type/offsets)
- *                 and per-slice copy tasks
- *   K5 copy     — partition-copy key/value bytes into per-shard contiguous
- *                 run segments (16-lane groups, dword funnel for unaligned
- *                 sources)
- *   K6 rundesc  — per-shard run descriptors, D2H to the host run registry
+ *                 record-boundary discovery, validation, totals, one 16-B
+ *                 emit record per update) + the per-block partial sums
+ *   K2 scan2    — exclusive prefix sums over (records, payload bytes) of the
+ *                 block sums; its thread 0 bump-reserves the tick's space in
+ *                 the device run store (ring or linear)
+ *   K3 emit     — 24-B record headers (seq/type/offsets) and per-slice copy
+ *                 tasks; its trailing blocks write the per-shard-group run
+ *                 descriptors, D2H to the host run registry
+ *   K4 copy     — partition-copy key/value bytes into per-shard contiguous
+ *                 run segments (part_copy.h)
+ *
+ * What a finished tick leaves of each shard group is host_store.h's ingest
+ * rule (gra::settle_group_locked); ingest_one only materialises the runs.
  *
  * The follower "memtable" is the device run store (288 GB HBM3E); the host
  * keeps descriptors only. Per-shard seq order is preserved because updates
@@ -765,15 +768,14 @@ struct GraEngine {
   std::mutex mu; /* engine-level: staging + tick enqueue + ingest */
   /* Arena maintenance. gra_reclaim moves the bytes of every listed device
    * run and rewrites hdr_cur / payload_cur, so an offset read under ss.mu is
-   * only good while no reclaim has run since. The rule for every reader that
-   * hands store offsets to a kernel or a copy:
-   *  - load store_epoch, snapshot the shard under ss.mu, take mu, compare;
-   *    when the epoch moved, drop mu and snapshot again (a whole new
-   *    snapshot: a run a compaction unlisted is not moved, and its bytes are
-   *    overwritten). With mu held no reclaim runs, so an unchanged epoch
-   *    vouches for the snapshot until mu is released;
-   *  - or snapshot under ss.mu with mu already held (lock order mu -> ss.mu,
-   *    the ingest path's).
+   * only good while no reclaim has run since. A reader that hands store
+   * offsets to a kernel or a copy gets them in one of two ways:
+   *  - through snapshot_shard(), which collects under ss.mu, takes mu and
+   *    compares the epoch it loaded first, again until they agree. With mu
+   *    held no reclaim runs, so an unchanged epoch vouches for the snapshot
+   *    until mu is released;
+   *  - or under ss.mu with mu already held (lock order mu -> ss.mu, the
+   *    ingest path's and fetch_listed_runs').
    * gra_reclaim bumps store_epoch AFTER the last shard's offsets are
    * rewritten: bumped first, a reader could pair the new epoch with an old
    * offset. gra_compact carries the offsets of its unlisted output run
@@ -1071,6 +1073,10 @@ int GraEngine::enqueue_tick(TickInput &in) {
     g_err = "tick exceeds max updates per tick";
     return GRA_ERR;
   }
+  if (in.counts.size() != n) { /* the ingest rule and the drain size need them */
+    g_err = "tick without per-update record counts";
+    return GRA_ERR;
+  }
   if (opts.drain_host && opts.store_ring && blob_bytes * 10 > opts.store_bytes) {
     /* same wrap hazard as the init-time guard, for replay ticks whose
      * size isn't bounded by staging_bytes */
@@ -1087,10 +1093,10 @@ int GraEngine::enqueue_tick(TickInput &in) {
   Slot &sl = slots[si];
   sl.busy = true;
   uint32_t ngroups = (uint32_t)groups.size();
-  /* the host copy is ALWAYS filled: ingest's corruption recovery walks
-   * sl.h_groups to find each group's update range (r01 bug: with a
-   * device-cached plan the host copy stayed stale and the error path read
-   * garbage groups — replay-tick corruption went undetected) */
+  /* the host copy is ALWAYS filled: ingest_one walks sl.h_groups to find
+   * each group's update range (r01 bug: with a device-cached plan the host
+   * copy stayed stale and corruption recovery read garbage groups —
+   * replay-tick corruption went undetected) */
   memcpy(sl.h_groups, groups.data(), ngroups * sizeof(GroupDesc));
   const GroupDesc *groups_for_kernel = in.d_groups ? in.d_groups : d_groups;
   uint32_t tick = tick_id++;
@@ -1100,8 +1106,19 @@ int GraEngine::enqueue_tick(TickInput &in) {
   t.n = n;
   t.ngroups = ngroups;
   t.blob_bytes = blob_bytes;
-  t.counts = std::move(in.counts);
+  t.counts = std::move(in.counts); /* n of them: every caller fills them */
   for (int i = 0; i < kEventsPerTick; i++) t.ev[i] = get_event();
+  /* a failed return below gives the slot and the events back: left busy,
+   * eight such failures would have free_slot spin on an empty pending list */
+  struct Release {
+    GraEngine *e;
+    TickRec *t;
+    ~Release() {
+      if (!t) return;
+      for (int i = 0; i < kEventsPerTick; i++) e->put_event(t->ev[i]);
+      e->slots[t->slot].busy = false;
+    }
+  } release{this, &t};
   static const bool detailed = env_flag("GRA_DETAILED_EVENTS");
 
   if (!in.d_groups) {
@@ -1220,12 +1237,11 @@ int GraEngine::enqueue_tick(TickInput &in) {
    * reported an error */
   HIP_TRY(hipMemcpyAsync(sl.h_place, place_slot, sizeof(TickPlace),
                          hipMemcpyDeviceToHost, copyout));
-  if (opts.drain_host && !t.counts.empty()) {
+  if (opts.drain_host) {
     /* drain the whole tick into a pinned host arena on the copyout stream,
      * overlapped with the next tick's kernels. Size bound: payload <=
      * blob + 7/record (cf re-prefix), + 15/record align pad + 24/record
-     * headers. Without counts (no record total) ingest falls back to the
-     * eager per-run fetch. */
+     * headers. */
     uint64_t recs = 0;
     for (uint32_t c : t.counts) recs += c;
     size_t need = (size_t)blob_bytes + 46 * recs + 80;
@@ -1238,6 +1254,7 @@ int GraEngine::enqueue_tick(TickInput &in) {
   }
   HIP_TRY(t.record(kEvPublished, copyout));
   pending.push_back(std::move(t));
+  release.t = nullptr; /* the tick owns them until ingest_one */
   return GRA_OK;
 }
 
@@ -1258,27 +1275,6 @@ static std::shared_ptr<Run> run_from(const DevRunDesc &rd, bool on_device) {
     run->payload_cur = rd.payload_off;
   }
   return run;
-}
-
-/* Roll the shard's submission seq back to the durable boundary and drop
- * retained-log entries past it: a batch that failed validation (or was
- * staged on top of one that did) must never be re-served downstream — the
- * reference's WAL only ever contains accepted batches. Caller holds ss.mu.
- *
- * Also the whole handling of a STALE group, on the error path and the
- * err==0 paths alike: a tick staged BEFORE a corrupt batch's failure was
- * detected carries base_seqs that assumed the corrupt batch applied. Such
- * ticks always ingest while the shard is still poisoned
- * (gra_handle_replicate_response's failure report drains pending ticks
- * before clearing the flag), so the group is dropped with durable_seq left
- * alone. Without this, durable_seq re-advances past the rolled-back boundary
- * and the failed batch is silently skipped on re-pull (follower divergence). */
-static void roll_back_locked(ShardState &ss) {
-  ss.next_seq = ss.durable_seq + 1;
-  while (!ss.log.empty() && ss.log.back().base_seq > ss.durable_seq) {
-    ss.log_used -= ss.log.back().rep.size();
-    ss.log.pop_back();
-  }
 }
 
 int GraEngine::ingest_one(TickRec &t, bool wait) {
@@ -1323,13 +1319,12 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
   stats.ticks += 1;
   stats.updates += t.n;
   stats.blob_bytes += t.blob_bytes;
-  uint32_t err = *sl.h_err;
   /* drain-host: back a run with its span of the tick's pinned arena
    * (k_drain streamed the whole tick there; kv_off stays tick-relative,
-   * pay_p = tick payload base). Falls back to the eager per-run fetch when
-   * the arena is absent (no counts / allocation failure). */
+   * pay_p = tick payload base). False when the arena could not be
+   * allocated. A kept run's tick was placed: h_place holds its offsets. */
   auto attach_drain = [&](Run &run, const DevRunDesc &rd) -> bool {
-    if (!t.drain_buf || sl.h_place->overflow) return false;
+    if (!t.drain_buf) return false;
     uint64_t hb16 =
         ((uint64_t)sl.h_place->total_rec * sizeof(wb::RecHdr) + 15) & ~15ull;
     run.hbuf = t.drain_buf;
@@ -1337,122 +1332,45 @@ int GraEngine::ingest_one(TickRec &t, bool wait) {
     run.pay_p = t.drain_buf.get() + hb16;
     return true;
   };
-  if (err != 0) {
-    /* Precise corruption recovery: fetch the per-update validity now (the
-     * slot and its d_ok belong to this tick until ingest returns, and the
-     * tick's kernels have retired, so a blocking copy reads its bytes; the
-     * clean path never pays for the download). Per shard, keep the prefix
-     * of records from updates BEFORE its first corrupt one (their seqs are
-     * final), drop the
-     * rest (their host-assigned seqs assumed the corrupt batch applied),
-     * roll the shard's seq back to the kept boundary and poison it — the
-     * reference's failed-apply -> re-pull-from-LatestSequenceNumber cadence
-     * (replicated_db.cpp:378-382). Groups are in tick order, so a later
-     * group of an already-poisoned shard is dropped whole. */
-    HIP_TRY(hipMemcpy(sl.h_ok, sl.d_ok, t.n, hipMemcpyDeviceToHost));
-    const bool have_counts = t.counts.size() == t.n;
-    for (uint32_t g = 0; g < t.ngroups; g++) {
-      DevRunDesc &rd = sl.h_rundescs[g];
-      const GroupDesc &gd = sl.h_groups[g];
-      ShardState &ss = shards[rd.shard];
-      std::lock_guard<std::mutex> lk(ss.mu);
-      if (rd.base_seq == 0) {
-        /* place overflow (store full in non-ring mode): NOTHING of this tick
-         * was applied — roll back to the durable boundary and poison; the
-         * condition persists until the operator gives the store room, like
-         * the reference's repeated DB::Write failures on a full disk
-         * (base_seq==0 is the discriminator: real seqs start at 1). */
-        ss.poisoned = true;
-        ss.cnt_failures++;
-        roll_back_locked(ss);
-        continue;
-      }
-      if (ss.poisoned) {
-        /* shard already failed (earlier this tick or a previous tick):
-         * everything staged after the failure is stale — drop the group
-         * without touching durable_seq (rd.base_seq-1 may sit past a seq
-         * hole), keep next_seq at the durable boundary, prune the log */
-        roll_back_locked(ss);
-        continue;
-      }
-      uint32_t keep_recs = 0;
-      uint64_t keep_seq = rd.base_seq - 1;
-      bool bad = false;
-      for (uint32_t i = 0; i < gd.n_upds; i++) {
-        if (!sl.h_ok[gd.first + i]) {
-          bad = true;
-          break;
-        }
-        uint32_t c = have_counts ? t.counts[gd.first + i] : 0;
-        keep_recs += c;
-        keep_seq += c;
-      }
-      if (!bad) { /* whole group clean */
-        auto run = run_from(rd, true);
-        if (opts.drain_host && !attach_drain(*run, rd))
-          (void)fetch_run_impl(this, *run);
-        if (rd.n_entries > 0 && !opts.store_ring) ss.runs.push_back(std::move(run));
-        if (rd.last_seq > ss.durable_seq) ss.durable_seq = rd.last_seq;
-        stats.records += rd.n_entries;
-        stats.payload_bytes += rd.payload_bytes;
-        continue;
-      }
-      if (keep_recs > 0 && have_counts && !opts.store_ring) {
-        /* truncated run: the leading clean records are contiguous */
-        auto run = run_from(rd, true);
-        run->last_seq = keep_seq;
-        run->n_entries = keep_recs; /* payload_bytes stays the whole group's:
-                                       an upper bound; fetch uses hdrs */
-        if (opts.drain_host && !attach_drain(*run, rd))
-          (void)fetch_run_impl(this, *run);
-        ss.runs.push_back(std::move(run));
-        stats.records += keep_recs;
-      }
-      if (keep_seq > ss.durable_seq) ss.durable_seq = keep_seq;
-      ss.poisoned = true;
-      ss.cnt_failures++; /* ≅ kReplicatorHandleResponseFailure */
-      roll_back_locked(ss);
+  /* The run of the records settle_group_locked kept, the leading ones of the
+   * group (payload_bytes stays the whole group's: an upper bound; a fetch
+   * goes by the headers). Linear store: a device run, with a host copy under
+   * drain_host (the drained span, else the eager D2H). Ring store: the
+   * device bytes recycle, so only ring + drain — the production drain shape
+   * — keeps a run, host-only, and only when the span is there (Get over
+   * recycled regions is undefined by contract). */
+  auto keep_run = [&](ShardState &ss, const DevRunDesc &rd,
+                      const GroupKeep &keep) {
+    if (keep.n_entries == 0 || (opts.store_ring && !opts.drain_host)) return;
+    auto run = run_from(rd, !opts.store_ring);
+    run->n_entries = keep.n_entries;
+    run->last_seq = keep.last_seq;
+    if (opts.drain_host && !attach_drain(*run, rd)) {
+      if (opts.store_ring) return;
+      (void)fetch_run_impl(this, *run);
     }
-  } else if (opts.store_ring) {
-    /* throughput store: runs are recycled by the ring; keep only seq/stats
-     * bookkeeping (Get over recycled regions is undefined by contract) */
-    for (uint32_t g = 0; g < t.ngroups; g++) {
-      DevRunDesc &rd = sl.h_rundescs[g];
-      ShardState &ss = shards[rd.shard];
-      std::lock_guard<std::mutex> lk(ss.mu);
-      if (ss.poisoned) { /* stale group, see roll_back_locked */
-        roll_back_locked(ss);
-        continue;
-      }
-      if (opts.drain_host && rd.n_entries > 0) {
-        /* ring + drain = the production drain shape: the device store is a
-         * staging ring, the host arena keeps the durable run */
-        auto run = run_from(rd, false);
-        if (attach_drain(*run, rd)) ss.runs.push_back(std::move(run));
-      }
-      if (rd.last_seq > ss.durable_seq) ss.durable_seq = rd.last_seq;
-      stats.records += rd.n_entries;
-      stats.payload_bytes += rd.payload_bytes;
-    }
-  } else {
-    for (uint32_t g = 0; g < t.ngroups; g++) {
-      DevRunDesc &rd = sl.h_rundescs[g];
-      ShardState &ss = shards[rd.shard];
-      std::lock_guard<std::mutex> lk(ss.mu);
-      if (ss.poisoned) { /* stale group, see roll_back_locked */
-        roll_back_locked(ss);
-        continue;
-      }
-      if (rd.n_entries > 0) {
-        auto run = run_from(rd, true);
-        if (opts.drain_host && !attach_drain(*run, rd))
-          (void)fetch_run_impl(this, *run); /* eager D2H fallback */
-        ss.runs.push_back(std::move(run));
-      }
-      if (rd.last_seq > ss.durable_seq) ss.durable_seq = rd.last_seq;
-      stats.records += rd.n_entries;
-      stats.payload_bytes += rd.payload_bytes;
-    }
+    ss.runs.push_back(std::move(run));
+  };
+  /* The per-update validity is fetched only when the tick reported an error
+   * (the slot and its d_ok belong to this tick until ingest returns, and the
+   * tick's kernels have retired, so a blocking copy reads its bytes; a clean
+   * tick never pays for the download). */
+  const bool failed = *sl.h_err != 0;
+  if (failed) HIP_TRY(hipMemcpy(sl.h_ok, sl.d_ok, t.n, hipMemcpyDeviceToHost));
+  /* groups in tick order: a later group of a shard poisoned by an earlier
+   * one is stale and dropped whole */
+  for (uint32_t g = 0; g < t.ngroups; g++) {
+    const DevRunDesc &rd = sl.h_rundescs[g];
+    const GroupDesc &gd = sl.h_groups[g];
+    ShardState &ss = shards[rd.shard];
+    std::lock_guard<std::mutex> lk(ss.mu);
+    const GroupKeep keep = settle_group_locked(
+        ss, {rd.base_seq, rd.last_seq, rd.n_entries,
+             failed ? sl.h_ok + gd.first : nullptr,
+             t.counts.data() + gd.first, gd.n_upds});
+    stats.records += keep.n_entries;
+    if (keep.whole) stats.payload_bytes += rd.payload_bytes;
+    keep_run(ss, rd, keep);
   }
   for (int i = 0; i < kEventsPerTick; i++) put_event(t.ev[i]);
   sl.busy = false;
@@ -1560,6 +1478,31 @@ int GraEngine::flush_locked() {
   if (rc != GRA_OK) return rc;
   HIP_TRY(hipStreamSynchronize(stream));
   return ingest(true);
+}
+
+/* The reader side of GraEngine::store_epoch, for every call that hands store
+ * offsets to a kernel or a copy. collect() runs under ss.mu and fills the
+ * caller's snapshot from ss.runs (clearing it first: it may run again);
+ * false = nothing for the device. Returns true with lk (e->mu) held and no
+ * gra_reclaim since the collect, so the offsets collected are good until lk
+ * is released; false, lk not held, when collect() returned false. When a
+ * reclaim ran between the collect and the lock the whole snapshot is taken
+ * again: a run a compaction unlisted is not moved, and its bytes are
+ * overwritten. */
+template <class F>
+static bool snapshot_shard(GraEngine *e, ShardState &ss,
+                           std::unique_lock<std::mutex> &lk, F collect) {
+  lk = std::unique_lock<std::mutex>(e->mu, std::defer_lock);
+  for (;;) { /* once, unless a gra_reclaim ran under the snapshot */
+    const uint64_t epoch = e->store_epoch.load(std::memory_order_acquire);
+    {
+      std::lock_guard<std::mutex> lk_shard(ss.mu);
+      if (!collect()) return false;
+    }
+    lk.lock();
+    if (e->store_epoch.load(std::memory_order_acquire) == epoch) return true;
+    lk.unlock();
+  }
 }
 
 /* ---------------- C ABI ---------------- */
@@ -1995,43 +1938,36 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
   std::vector<std::shared_ptr<Run>> host_runs, unbuilt;
   /* grow-only device staging cached on the engine (serialized with other
    * engine ops by mu; a serving deployment would shard this per stream) */
-  std::unique_lock<std::mutex> lk_engine(e->mu, std::defer_lock);
-  for (;;) { /* once, unless a gra_reclaim ran under the snapshot */
-    const uint64_t epoch = e->store_epoch.load(std::memory_order_acquire);
-    views.clear();
-    host_runs.clear();
-    unbuilt.clear();
-    {
-      std::lock_guard<std::mutex> lk(ss.mu);
-      views.reserve(ss.runs.size());
-      for (auto it = ss.runs.rbegin(); it != ss.runs.rend(); ++it) {
-        const Run &r = **it;
-        if (r.n_entries == 0) continue;
-        if (r.hdr_cur == UINT64_MAX) {
-          host_runs.push_back(*it); /* oldest..newest order irrelevant: probe
-                                       tracks max seqs */
-        } else {
-          views.push_back(view_of(r));
-          if (!r.kpref_built) unbuilt.push_back(*it); /* racy pre-filter:
-                                       re-checked under e->mu (rebuilds are
-                                       idempotent anyway) */
+  std::unique_lock<std::mutex> lk_engine;
+  if (!snapshot_shard(e, ss, lk_engine, [&] {
+        views.clear();
+        host_runs.clear();
+        unbuilt.clear();
+        views.reserve(ss.runs.size());
+        for (auto it = ss.runs.rbegin(); it != ss.runs.rend(); ++it) {
+          const Run &r = **it;
+          if (r.n_entries == 0) continue;
+          if (!r.on_device()) {
+            host_runs.push_back(*it); /* oldest..newest order irrelevant:
+                                         probe tracks max seqs */
+          } else {
+            views.push_back(view_of(r));
+            if (!r.kpref_built) unbuilt.push_back(*it); /* racy pre-filter:
+                                         re-checked under e->mu (rebuilds are
+                                         idempotent anyway) */
+          }
         }
+        return !views.empty();
+      })) {
+    if (host_runs.empty()) {
+      for (uint32_t q = 0; q < nq; q++) {
+        out[q].status = GRA_GET_MISS;
+        out[q].vlen = 0;
       }
+    } else { /* purely host-resident shard: answer via the host path */
+      for (uint32_t q = 0; q < nq; q++) out[q].status = GRA_GET_NEEDS_HOST;
     }
-    if (views.empty()) {
-      if (host_runs.empty()) {
-        for (uint32_t q = 0; q < nq; q++) {
-          out[q].status = GRA_GET_MISS;
-          out[q].vlen = 0;
-        }
-      } else { /* purely host-resident shard: answer via the host path */
-        for (uint32_t q = 0; q < nq; q++) out[q].status = GRA_GET_NEEDS_HOST;
-      }
-      return GRA_OK;
-    }
-    lk_engine.lock();
-    if (e->store_epoch.load(std::memory_order_acquire) == epoch) break;
-    lk_engine.unlock(); /* the offsets are stale (GraEngine::store_epoch) */
+    return GRA_OK;
   }
   size_t vb = (size_t)nq * val_stride;
   auto &mg = e->mg;
@@ -2235,10 +2171,7 @@ int gra_multiget(GraDb *db, uint32_t nq, const GraKeyRef *keys,
 
 /* ---- gra_scan: ordered range scan (≅ ApplicationDB::NewIterator) ---- */
 
-enum {
-  kScanTakeHostPath = 100, /* scan_device: not servable on device */
-  kScanStale = 101, /* scan_device: a gra_reclaim ran under the snapshot */
-};
+enum { kScanTakeHostPath = 100 }; /* scan_device: not servable on device */
 
 /* The scan chain's front end, shared by gra_scan and gra_compact (both run
  * it under e->mu on the shared ScCache): collect -> bitonic sort -> with a
@@ -2311,20 +2244,17 @@ static bool sc_launch_front(GraEngine *e, const std::vector<RunView> &views,
   return true;
 }
 
-/* Device path over a snapshot of device-resident runs, taken after
- * store_epoch read `epoch`. One sync to learn the page size, then the result
- * copy. Returns GRA_OK / GRA_BUF_TOO_SMALL / GRA_ERR, kScanTakeHostPath when
- * the tombstone list overflows or staging cannot be allocated, or kScanStale
- * (nothing launched) when the epoch has moved: the caller snapshots again. */
+/* Device path over a snapshot of device-resident runs that snapshot_shard
+ * vouches for: the caller holds e->mu. One sync to learn the page size, then
+ * the result copy. Returns GRA_OK / GRA_BUF_TOO_SMALL / GRA_ERR, or
+ * kScanTakeHostPath when the tombstone list overflows or staging cannot be
+ * allocated. */
 static int scan_device(GraEngine *e, const std::vector<RunView> &views,
                        bool sorted0, uint64_t total_payload, const uint8_t *lo,
                        uint32_t lo_len, const uint8_t *hi,
                        uint32_t hi_len, bool has_hi, uint32_t max_entries,
                        GraScanEntry *out, uint8_t *buf, size_t cap,
-                       GraScanInfo *info, uint64_t epoch) {
-  std::lock_guard<std::mutex> lk_engine(e->mu);
-  if (e->store_epoch.load(std::memory_order_acquire) != epoch)
-    return kScanStale;
+                       GraScanInfo *info) {
   auto &sc = e->sc;
   /* 0 = off (the default chain, kernel for kernel), 1 = concat, 2 = u64add */
   const int fold = !e->opts.fold_on_device              ? 0
@@ -2463,51 +2393,49 @@ int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
     int c = m ? memcmp(lo, hi, m) : 0;
     empty_range = c > 0 || (c == 0 && lo_len >= hi_len);
   }
-  /* snapshot the run list, as gra_multiget does (and again if a
-   * gra_reclaim ran under the snapshot: GraEngine::store_epoch) */
+  /* snapshot the run list, as gra_multiget does */
   std::vector<RunView> views;
   std::vector<std::shared_ptr<Run>> runs;
-  bool all_resident = true;
-  for (;;) {
-    const uint64_t epoch = e->store_epoch.load(std::memory_order_acquire);
-    bool any_host = false, sorted0 = false;
-    uint64_t dev_payload = 0;
+  bool all_resident = true, device_ok = false, sorted0 = false;
+  uint64_t dev_payload = 0;
+  std::unique_lock<std::mutex> lk_engine;
+  const bool on_device = snapshot_shard(e, ss, lk_engine, [&] {
+    bool any_host = false;
     views.clear();
     runs.clear();
     all_resident = true;
-    info->served_by = GRA_SCAN_DEVICE;
-    {
-      std::lock_guard<std::mutex> lk(ss.mu);
-      for (const auto &rp : ss.runs) {
-        if (rp->n_entries == 0) continue;
-        runs.push_back(rp);
-        all_resident = all_resident && rp->resident();
-        if (rp->hdr_cur == UINT64_MAX)
-          any_host = true;
-        else {
-          /* at most one sorted run, and it is the shard's oldest */
-          if (views.empty() && rp->sorted) sorted0 = true;
-          views.push_back(view_of(*rp));
-          dev_payload += rp->payload_bytes;
-        }
+    sorted0 = false;
+    dev_payload = 0;
+    for (const auto &rp : ss.runs) {
+      if (rp->n_entries == 0) continue;
+      runs.push_back(rp);
+      all_resident = all_resident && rp->resident();
+      if (!rp->on_device())
+        any_host = true;
+      else {
+        /* at most one sorted run, and it is the shard's oldest */
+        if (views.empty() && rp->sorted) sorted0 = true;
+        views.push_back(view_of(*rp));
+        dev_payload += rp->payload_bytes;
       }
     }
-    /* a shard whose device path would enter a sorted run says so for every
-     * range, the empty one included */
-    const bool device_ok = !any_host && views.size() <= 65535;
-    if (device_ok && sorted0) info->served_by = GRA_SCAN_DEVICE_INDEXED;
-    if (runs.empty() || empty_range) return GRA_OK;
-    if (!device_ok) break;
-    /* grid.y = one row per run. A stored key is shorter than kScMaxBound, so
-     * a longer bound orders against every key exactly as its first
-     * kScMaxBound bytes do */
+    /* grid.y = one row per run */
+    device_ok = !any_host && views.size() <= 65535;
+    return device_ok && !runs.empty() && !empty_range;
+  });
+  /* a shard whose device path would enter a sorted run says so for every
+   * range, the empty one included */
+  if (device_ok && sorted0) info->served_by = GRA_SCAN_DEVICE_INDEXED;
+  if (runs.empty() || empty_range) return GRA_OK;
+  if (on_device) {
+    /* A stored key is shorter than kScMaxBound, so a longer bound orders
+     * against every key exactly as its first kScMaxBound bytes do */
     uint32_t l32 = lo_len < kScMaxBound ? (uint32_t)lo_len : kScMaxBound;
     uint32_t h32 = hi_len < kScMaxBound ? (uint32_t)hi_len : kScMaxBound;
     int rc = scan_device(e, views, sorted0, dev_payload, lo, l32, hi, h32,
-                         has_hi, max_entries, out, buf, cap, info, epoch);
-    if (rc == kScanStale) continue;
+                         has_hi, max_entries, out, buf, cap, info);
     if (rc != kScanTakeHostPath) return rc;
-    break;
+    lk_engine.unlock(); /* fetch_listed_runs takes mu itself */
   }
   /* host path: host-origin runs in the shard (leader writes, drained
    * arenas), tombstone-list overflow, or no device staging */
@@ -2621,7 +2549,7 @@ int gra_compact(GraDb *db, GraCompactInfo *info) {
   {
     std::lock_guard<std::mutex> lk(ss.mu);
     for (const auto &rp : ss.runs) {
-      if (rp->hdr_cur == UINT64_MAX) break;
+      if (!rp->on_device()) break;
       snap.push_back(rp);
     }
     info->runs_after = (uint32_t)ss.runs.size();
@@ -2712,7 +2640,7 @@ int gra_store_usage(GraEngine *e, GraStoreUsage *out) {
   for (ShardState &ss : e->shards) {
     std::lock_guard<std::mutex> lk_shard(ss.mu);
     for (const auto &rp : ss.runs)
-      if (rp->hdr_cur != UINT64_MAX && rp->n_entries > 0)
+      if (rp->on_device() && rp->n_entries > 0)
         out->live += (uint64_t)rp->n_entries * sizeof(wb::RecHdr) +
                      rp->payload_bytes;
   }
@@ -2761,7 +2689,7 @@ int gra_reclaim(GraEngine *e, GraReclaimInfo *info) {
     ShardState &ss = e->shards[s];
     std::lock_guard<std::mutex> lk_shard(ss.mu);
     for (const auto &rp : ss.runs) {
-      if (rp->hdr_cur == UINT64_MAX || rp->n_entries == 0) continue;
+      if (!rp->on_device() || rp->n_entries == 0) continue;
       RcSegment h, p;
       h.src = rp->hdr_cur;
       h.nbytes = (uint64_t)rp->n_entries * sizeof(wb::RecHdr);
@@ -2888,35 +2816,28 @@ int gra_shard_checksum(GraDb *db, uint64_t *out) {
   ShardState &ss = e->shards[db->shard];
   std::vector<RunView> views;
   uint64_t host_sum = 0;
-  std::unique_lock<std::mutex> lk(e->mu, std::defer_lock);
-  for (;;) { /* once, unless a gra_reclaim ran under the snapshot */
-    const uint64_t epoch = e->store_epoch.load(std::memory_order_acquire);
-    views.clear();
-    host_sum = 0;
-    {
-      std::lock_guard<std::mutex> lk_shard(ss.mu);
-      for (const auto &rp : ss.runs) {
-        const Run &r = *rp;
-        if (r.n_entries == 0) continue;
-        if (r.hdr_cur == UINT64_MAX) { /* host-origin/drained: fold on host */
-          const wb::RecHdr *h = (const wb::RecHdr *)r.hdrs_data();
-          const uint8_t *pay = r.payload_data();
-          for (uint32_t i = 0; i < r.n_entries; i++)
-            host_sum += rec_hash_cs(h[i].seq, h[i].type, h[i].key_len,
-                                    h[i].val_len, pay + h[i].kv_off,
-                                    pay + h[i].kv_off + h[i].key_len);
-        } else {
-          views.push_back(view_of(r));
+  std::unique_lock<std::mutex> lk;
+  if (!snapshot_shard(e, ss, lk, [&] {
+        views.clear();
+        host_sum = 0;
+        for (const auto &rp : ss.runs) {
+          const Run &r = *rp;
+          if (r.n_entries == 0) continue;
+          if (!r.on_device()) { /* host-origin/drained: fold on host */
+            const wb::RecHdr *h = (const wb::RecHdr *)r.hdrs_data();
+            const uint8_t *pay = r.payload_data();
+            for (uint32_t i = 0; i < r.n_entries; i++)
+              host_sum += rec_hash_cs(h[i].seq, h[i].type, h[i].key_len,
+                                      h[i].val_len, pay + h[i].kv_off,
+                                      pay + h[i].kv_off + h[i].key_len);
+          } else {
+            views.push_back(view_of(r));
+          }
         }
-      }
-    }
-    if (views.empty()) {
-      *out = host_sum;
-      return GRA_OK;
-    }
-    lk.lock();
-    if (e->store_epoch.load(std::memory_order_acquire) == epoch) break;
-    lk.unlock(); /* the offsets are stale (GraEngine::store_epoch) */
+        return !views.empty();
+      })) {
+    *out = host_sum;
+    return GRA_OK;
   }
   DevBuf<RunView> d_runs; /* per call: freed on every return */
   DevBuf<unsigned long long> d_sum;

@@ -1,4 +1,5 @@
-/* host_store.cpp — run-format Get + leader-side host apply.
+/* host_store.cpp — run-format Get + leader-side host apply, the ingest rule
+ * and the plans of gra_compact / gra_reclaim.
  * Semantics cites: rocksdb_wrapper.cpp:5-8 (WriteToLeader = DB::Write),
  * rocksdb_assumption_test.cpp:136-187 (seq accounting). */
 #include "host_store.h"
@@ -67,6 +68,38 @@ void fold_value(bool have_base, const uint8_t *base, uint32_t base_len,
 }
 
 } /* namespace */
+
+void roll_back_locked(ShardState &ss) {
+  ss.next_seq = ss.durable_seq + 1;
+  while (!ss.log.empty() && ss.log.back().base_seq > ss.durable_seq) {
+    ss.log_used -= ss.log.back().rep.size();
+    ss.log.pop_back();
+  }
+}
+
+GroupKeep settle_group_locked(ShardState &ss, const GroupFacts &f) {
+  if (f.base_seq == 0 || ss.poisoned) { /* overflow / stale */
+    if (f.base_seq == 0) {
+      ss.poisoned = true;
+      ss.cnt_failures++;
+    }
+    roll_back_locked(ss);
+    return {0, 0, false};
+  }
+  GroupKeep keep = {f.n_entries, f.last_seq, true};
+  if (f.ok) {
+    uint32_t recs = 0, i = 0;
+    for (; i < f.n_upds && f.ok[i]; i++) recs += f.counts[i];
+    if (i < f.n_upds) keep = {recs, f.base_seq - 1 + recs, false};
+  }
+  if (keep.last_seq > ss.durable_seq) ss.durable_seq = keep.last_seq;
+  if (!keep.whole) {
+    ss.poisoned = true;
+    ss.cnt_failures++;
+    roll_back_locked(ss);
+  }
+  return keep;
+}
 
 int run_get(const std::vector<std::shared_ptr<Run>> &runs, const void *key_,
             size_t klen, int merge_op, std::string *out) {

@@ -48,6 +48,8 @@ struct Run {
   bool sorted = false; /* written by gra_compact / run_compact: one Put per
                           key, ascending bytewise key order, no tombstones.
                           A shard holds at most one, as its oldest run */
+  /* its bytes are in the store arena, at hdr_cur / payload_cur */
+  bool on_device() const { return hdr_cur != UINT64_MAX; }
   const uint8_t *hdrs_data() const { return hdr_p ? hdr_p : hdrs.data(); }
   const uint8_t *payload_data() const { return pay_p ? pay_p : payload.data(); }
   bool resident() const {
@@ -85,6 +87,56 @@ struct ShardState {
   std::atomic<uint64_t> cnt_served{0}, cnt_out_bytes{0};
   std::atomic<uint64_t> lat_sum_ms{0}, lat_n{0};
 };
+
+/* Roll the shard's submission seq back to the durable boundary and drop
+ * retained-log entries past it: a batch that failed validation (or was
+ * staged on top of one that did) must never be re-served downstream — the
+ * reference's WAL only ever contains accepted batches. Caller holds ss.mu. */
+void roll_back_locked(ShardState &ss);
+
+/* The ingest rule: what a finished tick leaves of ONE shard group, and what
+ * it does to the shard's seq state. Plain host arithmetic, so a CPU test
+ * holds every decision to account; the engine's ingest is one loop over a
+ * tick's groups (in tick order) that calls this under ss.mu and materialises
+ * the kept records as a run. */
+struct GroupFacts {
+  uint64_t base_seq, last_seq; /* from the run descriptor; base_seq == 0: the
+                                  tick found no room in the store */
+  uint32_t n_entries;
+  const uint8_t *ok;      /* the group's n_upds validity bytes, or nullptr:
+                             the tick reported no error */
+  const uint32_t *counts; /* the group's n_upds record counts */
+  uint32_t n_upds;
+};
+struct GroupKeep {
+  uint32_t n_entries; /* leading records of the group that stay readable */
+  uint64_t last_seq;  /* seq of the last of them */
+  bool whole;         /* the group was clean */
+};
+/*  - overflow (base_seq == 0; real seqs start at 1): NOTHING of the tick was
+ *    applied. Poison the shard, count a failure, roll back, keep nothing.
+ *    The condition persists until the operator gives the store room, like
+ *    the reference's repeated DB::Write failures on a full disk. k_scan2
+ *    raises the tick's error word wherever it sets the overflow flag the
+ *    descriptors get their base_seq == 0 from, so the case needs no `ok`;
+ *  - stale (the shard is already poisoned, by an earlier group of this tick
+ *    or an earlier tick): the group was staged BEFORE the failure was
+ *    detected and its base_seqs assumed the corrupt batch applied. Such
+ *    ticks always ingest while the shard is still poisoned
+ *    (gra_handle_replicate_response's failure report drains pending ticks
+ *    before clearing the flag). Roll back and keep nothing, durable_seq left
+ *    alone: advancing it would skip the failed batch on re-pull (follower
+ *    divergence);
+ *  - clean (no `ok`, or every byte set): keep the group whole,
+ *    durable_seq = max(durable_seq, last_seq);
+ *  - corrupt (first clear byte at update i): keep the records of the updates
+ *    before it — keep_recs = sum(counts[0..i)), their seqs are final, up to
+ *    keep_seq = base_seq - 1 + keep_recs — set durable_seq = max(durable_seq,
+ *    keep_seq), poison the shard, count a failure (≅
+ *    kReplicatorHandleResponseFailure) and roll back: the reference's
+ *    failed-apply -> re-pull-from-LatestSequenceNumber cadence
+ *    (replicated_db.cpp:378-382). */
+GroupKeep settle_group_locked(ShardState &ss, const GroupFacts &f);
 
 /* Get over a run list (newest last). merge_op: 0 concat, 1 u64add.
  * Returns 0 found, 1 not found. Found value appended to out. */

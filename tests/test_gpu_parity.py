@@ -512,10 +512,15 @@ def test_replay_parity_odd_shapes(olib, klen, vlen):
     e.close()
 
 
-def test_precise_corruption_truncation(olib):
+@pytest.mark.parametrize(
+    "mode", [{}, {"drain_host": 1}, {"store_ring": 1, "drain_host": 1}],
+    ids=["default", "drain", "ring_drain"])
+def test_precise_corruption_truncation(olib, mode):
     """A corrupt batch mid-tick must affect ONLY its shard, and that shard
-    keeps exactly the records from batches before the corrupt one."""
-    e = ra.Engine(nshards=3)
+    keeps exactly the records from batches before the corrupt one — in every
+    engine mode that keeps runs (the linear store, with and without the host
+    drain, and the ring store whose runs live in the drained host arenas)."""
+    e = ra.Engine(nshards=3, **mode)
     dbs = [e.open(s) for s in range(3)]
     ost = oracle_ffi.Store(olib, 3)
     # shard 0: clean stream; shard 1: good, good, BAD, good; shard 2: clean

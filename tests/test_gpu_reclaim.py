@@ -4,6 +4,8 @@ from the code under test: reads are compared with orc_get, checksums with
 orc_shard_checksum, and every byte figure (the cursor before, the bounds on
 the cursor after, the live bytes) is computed here from the parsed batches,
 as stored_bytes() in tests/test_gpu_compact.py does."""
+import threading
+
 import pytest
 
 import fold_model as fm
@@ -515,4 +517,80 @@ def test_reclaim_moves_a_truncated_run(monkeypatch, olib):
                                   else (MISS, b"")), (s, k)
         ents, _ = dbs[s].scan_page(b"", None, max_entries=1 << 10, cap=CAP)
         assert ents == [(k, vals[k]) for k in keys if vals[k] is not None]
+    e.close()
+
+
+# 6 ------------------------------------------- readers beside compact + reclaim
+
+def test_readers_beside_compact_and_reclaim(monkeypatch, olib):
+    """One shard of 300 Puts. The main thread runs 16 cycles of re-put one
+    key with the value it has, flush, compact, reclaim: every cycle moves the
+    shard's bytes and no read result ever changes. A reader thread meanwhile
+    alternates a multiget of all keys with a full scan and compares each with
+    the oracle's answers, taken once up front. It need not meet a stale
+    snapshot; what it pins down is that no reader is ever handed an offset a
+    reclaim has moved."""
+    small_copies(monkeypatch)
+    keys = [b"conc-key-%04d" % i for i in range(300)]
+    put = lambda i: PyBatch().put(  # noqa: E731
+        keys[i], bytes([i % 251]) * (20 + i % 90)).data()
+    e = ra.Engine(nshards=1, store_bytes=8 << 20, staging_bytes=16 << 20)
+    db, rdb = e.open(0), e.open(0)
+    ost = oracle_ffi.Store(olib, 1)
+    for t in range(3):
+        for i in range(100 * t, 100 * t + 100):
+            assert db.handle_replicate_response(put(i))
+            assert ost.apply(0, put(i))
+        e.flush()
+    want = oracle_values(ost, 0, keys)
+    assert all(v is not None for v in want.values())
+    want_mg = [(FOUND, want[k]) for k in keys]
+    want_scan = [(k, want[k]) for k in keys]  # keys ascend
+    stop, errors, rounds = threading.Event(), [], [0]
+
+    def reader():
+        try:
+            while True:
+                got = [(st, v) for st, _, v in rdb.multiget_raw(keys)]
+                if got != want_mg:
+                    bad = [k for k, g, w in zip(keys, got, want_mg) if g != w]
+                    errors.append("multiget round %d: %d keys differ, first %r"
+                                  % (rounds[0], len(bad), bad[0]))
+                    return
+                ents, info = rdb.scan_page(b"", None, max_entries=1 << 10,
+                                           cap=CAP)
+                if info.more or ents != want_scan:
+                    errors.append("scan round %d: %d entries, more=%d"
+                                  % (rounds[0], len(ents), info.more))
+                    return
+                rounds[0] += 1
+                if stop.is_set():
+                    return
+        except Exception as ex:  # a failed call is a failure of the test
+            errors.append(repr(ex))
+
+    th = threading.Thread(target=reader)
+    th.start()
+    moved = []
+    try:
+        for c in range(16):
+            i = (37 * c) % len(keys)
+            assert db.handle_replicate_response(put(i))
+            assert ost.apply(0, put(i))
+            e.flush()
+            assert db.compact().status == ra.GRA_COMPACT_DONE
+            info = e.reclaim()
+            moved.append(info.bytes_moved)
+            if errors:
+                break
+    finally:
+        stop.set()
+        th.join(timeout=60)
+    assert not th.is_alive()
+    print("reader rounds:", rounds[0], "bytes moved per cycle:", moved)
+    assert not errors, errors[0]
+    assert rounds[0] >= 1
+    assert len(moved) == 16 and sum(m > 0 for m in moved) >= 1
+    assert oracle_values(ost, 0, keys) == want  # the answers were fixed
+    assert db.latest_seq() == ost.latest_seq(0) == 300 + 16
     e.close()
