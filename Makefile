@@ -12,7 +12,7 @@ all: rocksplicator_amd/libgra.so oracle/libwb_oracle.so
 build:
 	mkdir -p build
 
-build/engine.o: $(CSRC)/engine.hip $(CSRC)/dev_buf.h $(CSRC)/part_copy.h $(CSRC)/mg_kernels.h $(CSRC)/scan_kernels.h $(CSRC)/compact_kernels.h $(CSRC)/reclaim_kernels.h $(CSRC)/fold.h $(CSRC)/wb_format.h $(CSRC)/host_store.h $(CSRC)/snappy.h include/rocksplicator_gpu.h | build
+build/engine.o: $(CSRC)/engine.hip $(CSRC)/dev_buf.h $(CSRC)/part_copy.h $(CSRC)/mg_kernels.h $(CSRC)/scan_kernels.h $(CSRC)/compact_kernels.h $(CSRC)/reclaim_kernels.h $(CSRC)/image_kernels.h $(CSRC)/fold.h $(CSRC)/wb_format.h $(CSRC)/host_store.h $(CSRC)/snappy.h include/rocksplicator_gpu.h | build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 build/host_store.o: $(CSRC)/host_store.cpp $(CSRC)/host_store.h $(CSRC)/wb_format.h | build

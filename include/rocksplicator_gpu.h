@@ -336,6 +336,106 @@ typedef struct {
 } GraReclaimInfo;
 int gra_reclaim(GraEngine *e, GraReclaimInfo *info);
 
+/* ---------------- shard images: bootstrap a replica past the log ----------
+ * ≅ the data-plane half of AdminHandler::async_tm_backupDB / restoreDB
+ * (rocksdb_admin/admin_handler.cpp:865-943): capture a consistent image of a
+ * shard, install it in an empty shard, and replication resumes from the
+ * image's sequence number instead of replaying a history the retained log
+ * (gra_get_updates) may no longer hold. An image built offline is installed
+ * the same way (≅ addS3SstFilesToDB, admin_handler.cpp:1635). The image is a
+ * byte string; storing and moving it (files, HDFS, S3) is the caller's.
+ *
+ * FORMAT, version 1, little-endian. A 64-byte header:
+ *    0  8 B  magic "GRASHIMG"           32  u64  payload_bytes (multiple of
+ *    8  u32  version = 1                         16, < 4 GiB)
+ *   12  u32  merge_op (GRA_MERGE_*)     40  u64  content_sum
+ *   16  u64  last_seq                   48  u64  reserved, 0
+ *   24  u64  n_entries (<= 2^30)        56  u64  header_sum: FNV-1a-64 over
+ *                                                bytes 0..55
+ * then n_entries record headers of 24 B (u64 seq | u32 kv_off | u32 val_len |
+ * u16 key_len | u8 type | u8 flags | u32 kpref), zero-padded to a multiple of
+ * 16, then payload_bytes of records: key bytes then value bytes at kv_off,
+ * each record padded with zeros to 16 B. image_bytes = 64 + align16(24 n) +
+ * payload_bytes. The records are what gra_compact would leave of the whole
+ * shard: one Put per live key (merge chains folded with merge_op, carrying
+ * the newest operand's seq), strictly ascending in gra_scan's order of the
+ * stored key. content_sum is gra_shard_checksum's definition over them;
+ * last_seq is the shard's durable seq at capture. Per entry i:
+ *   RECORD  type == 1 (Put), flags == 0, 1 <= seq <= last_seq,
+ *           val_len < 0xFFFF0000;
+ *   LAYOUT  kv_off a multiple of 16 and dense (kv_off[0] == 0, kv_off[i] ==
+ *           kv_off[i-1] + align16(key_len[i-1] + val_len[i-1])), the record
+ *           inside the payload, the last record ending at payload_bytes;
+ *   ORDER   key[i-1] < key[i].
+ * kpref (the 32-bit key fingerprint) is written by exporters and recomputed
+ * by importers, which ignore the stored value, as they ignore padding.
+ *
+ * VERDICT (GraImageInfo.reason; one rule for gra_image_check, the device
+ * check of gra_import and the tests): the header first — GRA_IMG_BAD_HEADER
+ * for fewer than 64 bytes, a wrong magic, version, header_sum, reserved word
+ * or unknown merge_op, then GRA_IMG_BAD_SIZE when a limit is exceeded or len
+ * is not image_bytes. Otherwise the failing entry with the lowest index
+ * decides (bad_index), RECORD before LAYOUT before ORDER. GRA_IMG_BAD_SUM
+ * only when every entry passes. */
+typedef struct {
+  uint32_t version, merge_op;
+  uint64_t last_seq, n_entries, payload_bytes, image_bytes, content_sum;
+  uint32_t reason;     /* GRA_IMG_* */
+  uint32_t served_by;  /* export only: 0 device chain, 1 host path */
+  uint64_t bad_index;  /* lowest failing entry, UINT64_MAX if none/header */
+} GraImageInfo;
+enum { GRA_IMG_OK, GRA_IMG_BAD_HEADER, GRA_IMG_BAD_SIZE, GRA_IMG_BAD_RECORD,
+       GRA_IMG_BAD_LAYOUT, GRA_IMG_BAD_ORDER, GRA_IMG_BAD_SUM };
+
+/* Capture ≅ ApplicationDBBackupManager / backupDBHelper's checkpoint
+ * (admin_handler.cpp:865-900). The call flushes (gra_flush), then takes the
+ * shard's run list and durable seq together; the image is what gra_compact
+ * would leave of the WHOLE run list, by its fold rules (chains of any length,
+ * the engine's merge operator whatever fold_on_device says). The store is
+ * untouched: no run is replaced, no read result or shard checksum changes,
+ * gra_store_usage().used is the same after the call.
+ *   served_by 0: every run is device-resident. gra_compact's device chain
+ *     writes the run into FREE arena space as scratch, it is checked and
+ *     summed there, copied to buf, and the cursor is put back. LIMIT, as for
+ *     gra_compact: the arena needs room for the output on top of its content;
+ *     GRA_FULL otherwise. Excludes gra_compact / gra_reclaim, and ticks wait,
+ *     for the duration.
+ *   served_by 1: the shard holds host-origin runs (a leader, drained arenas):
+ *     the runs are fetched and compacted on the host. Byte-identical to the
+ *     device chain's image for the same records.
+ * GRA_OK with info filled and info->image_bytes written to buf;
+ * GRA_BUF_TOO_SMALL when cap is too small, info->image_bytes exact (nothing
+ * written); GRA_FULL (above); GRA_ERR on a store_ring engine (it keeps no
+ * runs) and where gra_compact would report GRA_COMPACT_UNSUPPORTED —
+ * gra_last_error names the limit. An empty shard exports a valid 64-byte
+ * image. */
+int gra_export(GraDb *db, uint8_t *buf, size_t cap, GraImageInfo *info);
+
+/* Install ≅ restoreDBHelper (admin_handler.cpp:902-943: restore, reopen,
+ * then pull from the restored sequence number). Requires — GRA_ERR otherwise
+ * — an engine that is not store_ring, an image whose merge_op is the
+ * engine's, and a pristine shard: no runs, latest seq 0, not poisoned,
+ * nothing staged, an empty retained log. The header is checked on the host
+ * before anything is launched; the body is staged in device memory and
+ * proven well-formed THERE (the verdict rule above) before any reader can
+ * touch it; then the space is reserved from the store cursor (GRA_FULL when
+ * the arena has no room), headers and payload are placed, ONE sorted run is
+ * listed (all readers take it unchanged, gra_scan enters it by lower bound:
+ * GRA_SCAN_DEVICE_INDEXED) and the shard's durable and latest seq become
+ * last_seq, so a pull loop resumes with last_seq as its seq_no. An image
+ * without entries lists no run and still sets the seqs.
+ * A rejected image returns GRA_CORRUPT with info->reason / bad_index set and
+ * leaves shard and arena exactly as they were (used unchanged, no run,
+ * seq 0): a later good import into the same shard succeeds. Excludes
+ * gra_compact / gra_reclaim, and the shard's other calls wait, for the
+ * duration. */
+int gra_import(GraDb *db, const uint8_t *img, size_t len, GraImageInfo *info);
+
+/* The verdict rule on the host ≅ BackupEngine::VerifyBackup: no engine, no
+ * GPU. GRA_OK or GRA_CORRUPT with info->reason / bad_index. Never reads
+ * outside [img, img + len). */
+int gra_image_check(const uint8_t *img, size_t len, GraImageInfo *info);
+
 /* Full-store content checksum for any-size parity ("checksum of
  * checksums"): per record FNV-1a over (seq LE8 | type | key_len LE4 |
  * val_len LE4 | key bytes | val bytes), combined per shard by u64

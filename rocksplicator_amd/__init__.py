@@ -30,8 +30,20 @@ from .ffi import (  # noqa: F401
     GraReclaimInfo,
     GraStoreUsage,
     StoreFullError,
+    GRA_IMG_OK,
+    GRA_IMG_BAD_HEADER,
+    GRA_IMG_BAD_SIZE,
+    GRA_IMG_BAD_RECORD,
+    GRA_IMG_BAD_LAYOUT,
+    GRA_IMG_BAD_ORDER,
+    GRA_IMG_BAD_SUM,
+    GRA_IMG_NO_INDEX,
+    GraImageInfo,
+    ImageRejected,
+    image_check,
     MERGE_CONCAT,
     MERGE_U64ADD,
 )
+from .image import pack_image, unpack_image  # noqa: F401
 
 __version__ = "0.1.0"

@@ -492,6 +492,9 @@ __global__ void k_drain(const uint8_t *__restrict__ store,
 /* ---------------- arena reclaim (gra_reclaim) ---------------- */
 #include "reclaim_kernels.h"
 
+/* ---------------- shard images (gra_export / gra_import) ---------------- */
+#include "image_kernels.h"
+
 /* ---- full-store checksum (parity at any size) ----
  * Same record hash as the oracle's orc_shard_checksum: FNV-1a over
  * (seq LE8 | type | key_len LE4 | val_len LE4 | key | val), u64-ADD
@@ -788,6 +791,8 @@ struct GraEngine {
   DevBuf<uint8_t> rc_bounce; /* grow-only, allocated at the first reclaim
                                 that bounces; guarded by mu */
   DevBuf<RcTask> rc_tasks;
+  DevMirror<ImgCtl> img_ctl; /* gra_import / gra_export's result block;
+                                guarded by mu */
 
   int init(const GraEngineOpts &o);
   ~GraEngine();
@@ -2467,10 +2472,12 @@ int gra_scan(GraDb *db, const void *lo_, size_t lo_len, const void *hi_,
  * over the unbounded range with every merge chain folded, then
  * compact_kernels.h. The candidate buffers are sized up front from the
  * prefix's entry count, so there is no regrow pass; one D2H of the result
- * block and one sync. Returns GRA_OK with *res filled, or GRA_ERR. */
-static int compact_device(GraEngine *e, const std::vector<RunView> &views,
-                          bool sorted0, uint64_t total_entries, CpCtl *res) {
-  std::lock_guard<std::mutex> lk_engine(e->mu);
+ * block and one sync. Returns GRA_OK with *res filled, or GRA_ERR. The
+ * caller holds e->mu (gra_export keeps it until the cursor is put back). */
+static int compact_device_locked(GraEngine *e,
+                                 const std::vector<RunView> &views,
+                                 bool sorted0, uint64_t total_entries,
+                                 CpCtl *res) {
   auto &sc = e->sc;
   const int mode = e->opts.merge_op == GRA_MERGE_U64ADD ? 2 : 1;
   uint32_t cap = kScTile; /* power of two >= the prefix's entries */
@@ -2526,6 +2533,12 @@ static int compact_device(GraEngine *e, const std::vector<RunView> &views,
   }
   *res = *sc.cp.h;
   return GRA_OK;
+}
+
+static int compact_device(GraEngine *e, const std::vector<RunView> &views,
+                          bool sorted0, uint64_t total_entries, CpCtl *res) {
+  std::lock_guard<std::mutex> lk_engine(e->mu);
+  return compact_device_locked(e, views, sorted0, total_entries, res);
 }
 
 int gra_compact(GraDb *db, GraCompactInfo *info) {
@@ -2808,6 +2821,377 @@ int gra_reclaim(GraEngine *e, GraReclaimInfo *info) {
             ms(t_start, t_collected), segs.size(), ms(t_collected, t_planned),
             tasks.size(), launches.size(), ms(t_planned, t_copied),
             ms(t_copied, now()));
+  return GRA_OK;
+}
+
+/* ---- gra_export / gra_import / gra_image_check: shard images
+ * (≅ AdminHandler backupDB / restoreDB, the data-plane half) ---- */
+
+static_assert(GRA_IMG_OK == kImgOk && GRA_IMG_BAD_HEADER == kImgBadHeader &&
+                  GRA_IMG_BAD_SIZE == kImgBadSize &&
+                  GRA_IMG_BAD_RECORD == kImgBadRecord &&
+                  GRA_IMG_BAD_LAYOUT == kImgBadLayout &&
+                  GRA_IMG_BAD_ORDER == kImgBadOrder &&
+                  GRA_IMG_BAD_SUM == kImgBadSum,
+              "GRA_IMG_* mirror gra::kImg*");
+
+static void img_info_out(const ImageInfo &in, GraImageInfo *out) {
+  memset(out, 0, sizeof(*out));
+  out->version = in.version;
+  out->merge_op = in.merge_op;
+  out->last_seq = in.last_seq;
+  out->n_entries = in.n_entries;
+  out->payload_bytes = in.payload_bytes;
+  out->image_bytes = in.image_bytes;
+  out->content_sum = in.content_sum;
+  out->reason = in.reason;
+  out->bad_index = in.bad_index;
+}
+
+static const char *img_reason_name(uint32_t r) {
+  static const char *names[] = {"ok",         "bad header", "bad size",
+                                "bad record", "bad layout", "bad key order",
+                                "bad content sum"};
+  return r < 7 ? names[r] : "?";
+}
+
+int gra_image_check(const uint8_t *img, size_t len, GraImageInfo *info) {
+  if (!info || (len && !img)) {
+    g_err = "gra_image_check: null argument";
+    return GRA_ERR;
+  }
+  ImageInfo ii;
+  check_image(img, len, &ii);
+  img_info_out(ii, info);
+  if (ii.reason == kImgOk) return GRA_OK;
+  g_err = std::string("gra_image_check: ") + img_reason_name(ii.reason);
+  return GRA_CORRUPT;
+}
+
+/* k_img_check over n entries at hdrs / pay (device pointers), the result
+ * block zeroed first. Caller holds e->mu; launch errors are the caller's
+ * hipGetLastError. */
+static bool img_launch_check(GraEngine *e, const uint8_t *hdrs,
+                             const uint8_t *pay, uint64_t n,
+                             uint64_t payload_bytes, uint64_t last_seq) {
+  ImgCtl zero = {};
+  zero.verdict = kImgClean;
+  /* pinned: the copy reads it in stream order, and the next write to it is
+   * the caller's D2H of the result on the same stream */
+  *e->img_ctl.h = zero;
+  if (hipMemcpyAsync(e->img_ctl.d, e->img_ctl.h, sizeof(ImgCtl),
+                     hipMemcpyHostToDevice, e->stream) != hipSuccess)
+    return false;
+  hipLaunchKernelGGL(k_img_check, dim3((uint32_t)((n + 255) / 256)), dim3(256),
+                     0, e->stream, (const wb::RecHdr *)hdrs, pay, n,
+                     payload_bytes, last_seq, e->img_ctl.d);
+  return true;
+}
+
+int gra_export(GraDb *db, uint8_t *buf, size_t cap, GraImageInfo *info) {
+  if (!db || !info || (cap && !buf)) {
+    g_err = "gra_export: null argument";
+    return GRA_ERR;
+  }
+  memset(info, 0, sizeof(*info));
+  info->bad_index = kImgNoIndex;
+  GraEngine *e = db->e;
+  if (e->opts.store_ring) {
+    g_err = "gra_export: a store_ring engine keeps no runs";
+    return GRA_ERR;
+  }
+  ShardState &ss = e->shards[db->shard];
+  const uint32_t merge_op = (uint32_t)e->opts.merge_op;
+  /* as gra_compact: no gra_reclaim (and no other compaction's reservation)
+   * between the snapshot and the cursor's restore */
+  std::lock_guard<std::mutex> lk_maint(e->maint_mu);
+  std::unique_lock<std::mutex> lk_engine(e->mu);
+  int rc = e->flush_locked();
+  if (rc != GRA_OK) return rc;
+  /* the run list and the durable seq, together; host copies of host-path
+   * runs are fetched under the same two locks (fetch_listed_runs' order) */
+  std::vector<std::shared_ptr<Run>> snap;
+  uint64_t last_seq = 0;
+  bool all_device = true;
+  {
+    std::lock_guard<std::mutex> lk(ss.mu);
+    last_seq = ss.durable_seq;
+    for (const auto &rp : ss.runs) {
+      if (rp->n_entries == 0) continue;
+      snap.push_back(rp);
+      all_device = all_device && rp->on_device();
+    }
+    if (!all_device)
+      for (const auto &rp : snap) {
+        rc = fetch_run_impl(e, *rp);
+        if (rc != GRA_OK) return rc;
+      }
+  }
+  info->version = kImgVersion;
+  info->merge_op = merge_op;
+  info->last_seq = last_seq;
+  auto too_small = [&](uint64_t need) {
+    info->image_bytes = need;
+    if (cap >= need) return false;
+    g_err = "gra_export: buffer too small for the image";
+    return true;
+  };
+  if (snap.empty()) { /* an empty shard: the header alone */
+    if (too_small(kImgHeaderBytes)) return GRA_BUF_TOO_SMALL;
+    image_write_header(buf, merge_op, last_seq, 0, 0, 0);
+    return GRA_OK;
+  }
+  if (!all_device) {
+    /* host path: the host copies stay valid wherever the device bytes go */
+    lk_engine.unlock();
+    info->served_by = 1;
+    Run out;
+    if (run_compact(snap, (int)merge_op, &out) != 0) {
+      g_err = "gra_export: unsupported shard (more than 4096 range tombstones "
+              "or 2^30 entries, a payload of 4 GiB or a value of 0xFFFF0000 "
+              "bytes), as for gra_compact";
+      return GRA_ERR;
+    }
+    std::vector<uint8_t> img;
+    image_from_run(out, last_seq, merge_op, &img);
+    ImageInfo ii;
+    if (check_image(img.data(), img.size(), &ii) != kImgOk) {
+      g_err = std::string("gra_export: the image failed its own check: ") +
+              img_reason_name(ii.reason);
+      return GRA_ERR;
+    }
+    info->n_entries = ii.n_entries;
+    info->payload_bytes = ii.payload_bytes;
+    info->content_sum = ii.content_sum;
+    if (too_small(img.size())) return GRA_BUF_TOO_SMALL;
+    memcpy(buf, img.data(), img.size());
+    return GRA_OK;
+  }
+  /* device chain: gra_compact's, into free arena space as scratch */
+  std::vector<RunView> views;
+  uint64_t entries_in = 0;
+  for (const auto &rp : snap) {
+    views.push_back(view_of(*rp));
+    entries_in += rp->n_entries;
+  }
+  if (entries_in > kImgMaxEntries) {
+    g_err = "gra_export: unsupported shard (more than 2^30 entries)";
+    return GRA_ERR;
+  }
+  if (!e->img_ctl.ensure()) {
+    g_err = "gra_export: device staging allocation failed";
+    return GRA_ERR;
+  }
+  CpCtl cp;
+  rc = compact_device_locked(e, views, snap[0]->sorted, entries_in, &cp);
+  if (rc != GRA_OK) return rc;
+  if (cp.unsupported) { /* nothing reserved */
+    g_err = "gra_export: unsupported shard (more than 4096 range tombstones, "
+            "a payload of 4 GiB or a value of 0xFFFF0000 bytes), as for "
+            "gra_compact";
+    return GRA_ERR;
+  }
+  if (cp.overflow) { /* nothing reserved */
+    g_err = "gra_export: the store arena has no scratch room for the image";
+    return GRA_FULL;
+  }
+  /* from here the cursor is past the scratch run: every return puts it back,
+   * stream-ordered behind the chain, before e->mu is released (no tick, no
+   * compaction has reserved in between: both need e->mu or maint_mu) */
+  const uint64_t n = cp.n_out, pb = cp.payload_bytes;
+  const uint64_t hb = img_align16(n * sizeof(wb::RecHdr));
+  const uint64_t need = kImgHeaderBytes + hb + pb;
+  hipStream_t st = e->stream;
+  bool ok = true, fits = !too_small(need);
+  if (fits && n > 0) {
+    ok = img_launch_check(e, e->d_store + cp.hdr_off,
+                          e->d_store + cp.payload_off, n, pb, last_seq) &&
+         hipGetLastError() == hipSuccess &&
+         hipMemcpyAsync(e->img_ctl.h, e->img_ctl.d, sizeof(ImgCtl),
+                        hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipMemcpyAsync(buf + kImgHeaderBytes, e->d_store + cp.hdr_off,
+                        n * sizeof(wb::RecHdr), hipMemcpyDeviceToHost,
+                        st) == hipSuccess &&
+         (pb == 0 ||
+          hipMemcpyAsync(buf + kImgHeaderBytes + hb,
+                         e->d_store + cp.payload_off, pb,
+                         hipMemcpyDeviceToHost, st) == hipSuccess);
+  }
+  const uint64_t old_cursor = cp.hdr_off;
+  ok = hipMemcpyAsync(e->d_cursor, &old_cursor, 8, hipMemcpyHostToDevice,
+                      st) == hipSuccess && ok;
+  ok = hipStreamSynchronize(st) == hipSuccess && ok;
+  if (!ok) {
+    g_err = "gra_export: device op failed";
+    return GRA_ERR;
+  }
+  lk_engine.unlock();
+  info->n_entries = n;
+  info->payload_bytes = pb;
+  if (!fits) return GRA_BUF_TOO_SMALL;
+  uint64_t sum = 0;
+  if (n > 0) {
+    const ImgCtl &r = *e->img_ctl.h; /* maint_mu still keeps other users out */
+    if (r.verdict != kImgClean) {
+      g_err = std::string("gra_export: the image failed its own check: ") +
+              img_reason_name((uint32_t)(r.verdict & 7));
+      return GRA_ERR;
+    }
+    sum = r.sum;
+    /* the apply path writes key and value only: padding is whatever the
+     * arena held. An image's padding is 0 */
+    uint8_t *hdrs = buf + kImgHeaderBytes, *pay = hdrs + hb;
+    memset(hdrs + n * sizeof(wb::RecHdr), 0, hb - n * sizeof(wb::RecHdr));
+    for (uint64_t i = 0; i < n; i++) {
+      wb::RecHdr h;
+      memcpy(&h, hdrs + i * sizeof(wb::RecHdr), sizeof(h));
+      const uint64_t end = (uint64_t)h.kv_off + h.key_len + h.val_len;
+      memset(pay + end, 0, img_align16(end) - end);
+    }
+  }
+  info->content_sum = sum;
+  image_write_header(buf, merge_op, last_seq, n, pb, sum);
+  return GRA_OK;
+}
+
+int gra_import(GraDb *db, const uint8_t *img, size_t len, GraImageInfo *info) {
+  if (!db || !info || (len && !img)) {
+    g_err = "gra_import: null argument";
+    return GRA_ERR;
+  }
+  GraEngine *e = db->e;
+  ImageInfo ii;
+  check_image_header(img, len, &ii);
+  img_info_out(ii, info);
+  if (e->opts.store_ring) {
+    g_err = "gra_import: a store_ring engine keeps no runs";
+    return GRA_ERR;
+  }
+  if (ii.reason != kImgOk) { /* before any launch */
+    g_err = std::string("gra_import: ") + img_reason_name(ii.reason);
+    return GRA_CORRUPT;
+  }
+  if (ii.merge_op != (uint32_t)e->opts.merge_op) {
+    g_err = "gra_import: the image was folded with another merge operator "
+            "than the engine's";
+    return GRA_ERR;
+  }
+  if (ii.last_seq == ~0ull) {
+    g_err = "gra_import: last_seq leaves no seq to resume with";
+    return GRA_ERR;
+  }
+  ShardState &ss = e->shards[db->shard];
+  /* maint_mu from before the reservation to the listing, as gra_compact; mu
+   * for the stream and the cursor; ss.mu so the shard stays pristine until
+   * the run is listed (lock order maint_mu -> mu -> ss.mu) */
+  std::lock_guard<std::mutex> lk_maint(e->maint_mu);
+  std::lock_guard<std::mutex> lk_engine(e->mu);
+  std::lock_guard<std::mutex> lk(ss.mu);
+  if (!ss.runs.empty() || ss.next_seq != 1 || ss.durable_seq != 0 ||
+      ss.poisoned || !ss.log.empty()) {
+    g_err = "gra_import: the shard is not pristine (it holds runs, seqs, "
+            "staged updates or a retained log)";
+    return GRA_ERR;
+  }
+  const uint64_t n = ii.n_entries, pb = ii.payload_bytes;
+  if (n == 0) { /* nothing for the device: the sum of no record is 0 */
+    if (ii.content_sum != 0) {
+      info->reason = kImgBadSum;
+      g_err = "gra_import: bad content sum";
+      return GRA_CORRUPT;
+    }
+    ss.durable_seq = ii.last_seq;
+    ss.next_seq = ii.last_seq + 1;
+    return GRA_OK;
+  }
+  /* GRA_IMAGE_TIMING=1: the call's phases on stderr (scripts/bench_image.py
+   * sets it, to tell the H2D copy from the check and the placement) */
+  static const bool timing = env_flag("GRA_IMAGE_TIMING");
+  const uint64_t hb = img_align16(n * sizeof(wb::RecHdr));
+  const uint64_t body = hb + pb;
+  DevBuf<uint8_t> d_img; /* per call: freed on every return */
+  if (!e->img_ctl.ensure() || !d_img.reserve_bytes(body + 16)) {
+    g_err = "gra_import: device staging allocation failed";
+    return GRA_ERR;
+  }
+  hipStream_t st = e->stream;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (timing)
+    for (auto &x : ev) (void)hipEventCreate(&x);
+  auto mark = [&](int i) {
+    if (timing) (void)hipEventRecord(ev[i], st);
+  };
+  const uint8_t *d_hdrs = d_img.get(), *d_pay = d_img.get() + hb;
+  bool ok = false;
+  do {
+    mark(0);
+    if (hipMemcpyAsync(d_img.get(), img + kImgHeaderBytes, body,
+                       hipMemcpyHostToDevice, st) != hipSuccess)
+      break;
+    mark(1);
+    if (!img_launch_check(e, d_hdrs, d_pay, n, pb, ii.last_seq)) break;
+    hipLaunchKernelGGL(k_img_reserve, dim3(1), dim3(64), 0, st, e->img_ctl.d,
+                       n, pb, ii.content_sum, e->d_cursor,
+                       (uint64_t)e->opts.store_bytes);
+    mark(2);
+    /* one block per 256 uint4s or entries, capped: the kernel strides */
+    uint64_t work = (pb >> 4) > n ? (pb >> 4) : n;
+    uint64_t nblk = (work + 255) / 256;
+    hipLaunchKernelGGL(k_img_place, dim3(nblk < 4096 ? (uint32_t)nblk : 4096),
+                       dim3(256), 0, st, e->d_store, e->img_ctl.d,
+                       (const wb::RecHdr *)d_hdrs, d_pay, n, pb);
+    mark(3);
+    if (hipGetLastError() != hipSuccess) break;
+    if (hipMemcpyAsync(e->img_ctl.h, e->img_ctl.d, sizeof(ImgCtl),
+                       hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      break;
+    ok = true;
+  } while (0);
+  if (timing) {
+    if (ok) {
+      float h2d = 0, chk = 0, place = 0;
+      (void)hipEventElapsedTime(&h2d, ev[0], ev[1]);
+      (void)hipEventElapsedTime(&chk, ev[1], ev[2]);
+      (void)hipEventElapsedTime(&place, ev[2], ev[3]);
+      fprintf(stderr,
+              "[gra] import: %llu entries, %llu bytes: h2d %.3f ms, check+"
+              "reserve %.3f ms, place %.3f ms\n",
+              (unsigned long long)n, (unsigned long long)body, h2d, chk,
+              place);
+    }
+    for (auto &x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+  if (!ok) {
+    (void)hipStreamSynchronize(st);
+    g_err = "gra_import: device op failed";
+    return GRA_ERR;
+  }
+  const ImgCtl &r = *e->img_ctl.h;
+  if (r.reason != kImgOk) {
+    info->reason = r.reason;
+    if (r.verdict != kImgClean) info->bad_index = r.verdict >> 3;
+    g_err = std::string("gra_import: ") + img_reason_name(r.reason);
+    return GRA_CORRUPT;
+  }
+  if (r.overflow) {
+    g_err = "gra_import: the store arena cannot hold the image";
+    return GRA_FULL;
+  }
+  auto run = std::make_shared<Run>();
+  run->base_seq = 1;
+  run->last_seq = ii.last_seq;
+  run->n_entries = (uint32_t)n;
+  run->payload_bytes = (uint32_t)pb;
+  run->hdr_cur = r.hdr_off;
+  run->payload_cur = r.payload_off;
+  run->pay_rel_base = 0;
+  run->kpref_built = true; /* k_img_place filled every header's fingerprint */
+  run->sorted = true;
+  ss.runs.push_back(std::move(run));
+  ss.durable_seq = ii.last_seq;
+  ss.next_seq = ii.last_seq + 1;
   return GRA_OK;
 }
 

@@ -371,6 +371,147 @@ int run_compact(const std::vector<std::shared_ptr<Run>> &runs, int merge_op,
   return 0;
 }
 
+/* ---- shard images: the host statement of the format and its verdict rule
+ * (host_store.h) ---- */
+
+namespace {
+
+const char kImgMagic[8] = {'G', 'R', 'A', 'S', 'H', 'I', 'M', 'G'};
+
+uint64_t fnv64(const uint8_t *p, size_t n) {
+  uint64_t h = 1469598103934665603ULL;
+  for (size_t i = 0; i < n; i++) h = (h ^ p[i]) * 1099511628211ULL;
+  return h;
+}
+
+uint64_t rd64(const uint8_t *p) { return wb::fixed64_le(p); }
+uint32_t rd32(const uint8_t *p) { return wb::fixed32_le(p); }
+void wr64(uint8_t *p, uint64_t v) {
+  for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+void wr32(uint8_t *p, uint32_t v) {
+  for (int i = 0; i < 4; i++) p[i] = (uint8_t)(v >> (8 * i));
+}
+
+} /* namespace */
+
+uint64_t rec_hash_host(uint64_t seq, uint8_t type, uint32_t klen, uint32_t vlen,
+                       const uint8_t *key, const uint8_t *val) {
+  uint8_t pre[17];
+  wr64(pre, seq);
+  pre[8] = type;
+  wr32(pre + 9, klen);
+  wr32(pre + 13, vlen);
+  uint64_t h = 1469598103934665603ULL;
+  for (size_t i = 0; i < sizeof(pre); i++) h = (h ^ pre[i]) * 1099511628211ULL;
+  for (uint32_t i = 0; i < klen; i++) h = (h ^ key[i]) * 1099511628211ULL;
+  for (uint32_t i = 0; i < vlen; i++) h = (h ^ val[i]) * 1099511628211ULL;
+  return h;
+}
+
+void image_write_header(uint8_t *dst, uint32_t merge_op, uint64_t last_seq,
+                        uint64_t n_entries, uint64_t payload_bytes,
+                        uint64_t content_sum) {
+  memcpy(dst, kImgMagic, 8);
+  wr32(dst + 8, kImgVersion);
+  wr32(dst + 12, merge_op);
+  wr64(dst + 16, last_seq);
+  wr64(dst + 24, n_entries);
+  wr64(dst + 32, payload_bytes);
+  wr64(dst + 40, content_sum);
+  wr64(dst + 48, 0);
+  wr64(dst + 56, fnv64(dst, 56));
+}
+
+uint32_t check_image_header(const uint8_t *img, size_t len, ImageInfo *out) {
+  *out = ImageInfo();
+  auto verdict = [&](uint32_t r) { return out->reason = r; };
+  if (!img || len < kImgHeaderBytes) return verdict(kImgBadHeader);
+  if (memcmp(img, kImgMagic, 8) != 0) return verdict(kImgBadHeader);
+  out->version = rd32(img + 8);
+  out->merge_op = rd32(img + 12);
+  if (out->version != kImgVersion || rd64(img + 56) != fnv64(img, 56) ||
+      rd64(img + 48) != 0 || out->merge_op > 1)
+    return verdict(kImgBadHeader);
+  out->last_seq = rd64(img + 16);
+  out->n_entries = rd64(img + 24);
+  out->payload_bytes = rd64(img + 32);
+  out->content_sum = rd64(img + 40);
+  if (out->n_entries > kImgMaxEntries || (out->payload_bytes & 15) ||
+      out->payload_bytes >= (1ull << 32) ||
+      (out->n_entries == 0 && out->payload_bytes != 0))
+    return verdict(kImgBadSize);
+  out->image_bytes = kImgHeaderBytes +
+                     img_align16(out->n_entries * sizeof(wb::RecHdr)) +
+                     out->payload_bytes;
+  if ((uint64_t)len != out->image_bytes) return verdict(kImgBadSize);
+  return verdict(kImgOk);
+}
+
+uint32_t check_image(const uint8_t *img, size_t len, ImageInfo *out) {
+  if (check_image_header(img, len, out) != kImgOk) return out->reason;
+  const uint64_t n = out->n_entries, pb = out->payload_bytes;
+  const uint8_t *hdrs = img + kImgHeaderBytes;
+  const uint8_t *pay = hdrs + img_align16(n * sizeof(wb::RecHdr));
+  uint64_t sum = 0;
+  wb::RecHdr prev = {};
+  bool prev_in = false;
+  for (uint64_t i = 0; i < n; i++) {
+    wb::RecHdr h; /* the image may sit at any alignment */
+    memcpy(&h, hdrs + i * sizeof(wb::RecHdr), sizeof(h));
+    const uint64_t bytes = (uint64_t)h.key_len + h.val_len;
+    const bool in = (uint64_t)h.kv_off + bytes <= pb;
+    uint32_t bad = kImgOk;
+    if (h.type != wb::kValue || h.flags != 0 || h.seq < 1 ||
+        h.seq > out->last_seq || h.val_len >= 0xFFFF0000u) {
+      bad = kImgBadRecord;
+    } else {
+      const uint64_t want =
+          i == 0 ? 0
+                 : (uint64_t)prev.kv_off +
+                       img_align16((uint64_t)prev.key_len + prev.val_len);
+      if ((h.kv_off & 15) || h.kv_off != want || !in ||
+          (i == n - 1 && (uint64_t)h.kv_off + img_align16(bytes) != pb))
+        bad = kImgBadLayout;
+      else if (i > 0 && prev_in &&
+               key_cmp(pay + prev.kv_off, prev.key_len, pay + h.kv_off,
+                       h.key_len) >= 0)
+        bad = kImgBadOrder;
+    }
+    if (bad != kImgOk) {
+      out->bad_index = i;
+      return out->reason = bad;
+    }
+    sum += rec_hash_host(h.seq, h.type, h.key_len, h.val_len, pay + h.kv_off,
+                         pay + h.kv_off + h.key_len);
+    prev = h;
+    prev_in = in;
+  }
+  if (sum != out->content_sum) return out->reason = kImgBadSum;
+  return out->reason = kImgOk;
+}
+
+void image_from_run(const Run &run, uint64_t last_seq, uint32_t merge_op,
+                    std::vector<uint8_t> *out) {
+  const uint64_t n = run.n_entries;
+  const uint64_t hb = img_align16(n * sizeof(wb::RecHdr));
+  out->assign(kImgHeaderBytes + hb + run.payload_bytes, 0);
+  uint8_t *hdrs = out->data() + kImgHeaderBytes, *pay = hdrs + hb;
+  if (n) memcpy(hdrs, run.hdrs_data(), n * sizeof(wb::RecHdr));
+  uint64_t sum = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    wb::RecHdr h;
+    memcpy(&h, hdrs + i * sizeof(wb::RecHdr), sizeof(h));
+    const uint8_t *src = run.payload_data() + h.kv_off;
+    /* key and value only: the padding stays 0 */
+    memcpy(pay + h.kv_off, src, (size_t)h.key_len + h.val_len);
+    sum += rec_hash_host(h.seq, h.type, h.key_len, h.val_len, src,
+                         src + h.key_len);
+  }
+  image_write_header(out->data(), merge_op, last_seq, n, run.payload_bytes,
+                     sum);
+}
+
 bool host_build_run(const uint8_t *rep, size_t len, uint64_t base_seq, Run *out) {
   wb::WalkTotals tot = wb::walk(rep, (uint32_t)len, nullptr, 0);
   if (!tot.ok) return false;

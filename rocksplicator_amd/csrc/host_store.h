@@ -190,6 +190,99 @@ int run_scan(const std::vector<std::shared_ptr<Run>> &runs, const void *lo,
 int run_compact(const std::vector<std::shared_ptr<Run>> &runs, int merge_op,
                 Run *out);
 
+/* ---- shard images (gra_export / gra_import / gra_image_check) ----
+ *
+ * A shard image is what run_compact leaves of a shard — one Put per live
+ * key, key-sorted, in the store's own layout — behind a 64-byte header.
+ * Version 1, little-endian:
+ *
+ *    0  8 B  magic "GRASHIMG"
+ *    8  u32  version = 1
+ *   12  u32  merge_op (GRA_MERGE_* the values were folded with)
+ *   16  u64  last_seq: the shard's durable seq at capture; the importer
+ *            resumes from it
+ *   24  u64  n_entries (<= 2^30)
+ *   32  u64  payload_bytes (multiple of 16, < 4 GiB)
+ *   40  u64  content_sum: rec_hash_cs of every record, summed mod 2^64 (what
+ *            gra_shard_checksum reports for a shard holding just the image)
+ *   48  u64  reserved, 0
+ *   56  u64  header_sum: FNV-1a-64 over bytes 0..55
+ *   64  n_entries x wb::RecHdr (24 B), zero-padded to a multiple of 16
+ *       payload_bytes of records
+ *
+ * image_bytes = 64 + align16(24 n) + payload_bytes. Rules per entry i:
+ *   RECORD  type == kValue, flags == 0, 1 <= seq <= last_seq,
+ *           val_len < 0xFFFF0000;
+ *   LAYOUT  kv_off is a multiple of 16 and dense: kv_off[0] == 0, kv_off[i] ==
+ *           kv_off[i-1] + align16(key_len[i-1] + val_len[i-1]) (64-bit);
+ *           kv_off + key_len + val_len <= payload_bytes (in bounds); the last
+ *           entry's kv_off + align16(key_len + val_len) == payload_bytes;
+ *   ORDER   key[i-1] < key[i] in gra_scan's order (memcmp on the common
+ *           prefix, the shorter key first, over the stored key). Looked at
+ *           only when entries i and i-1 are both in bounds: an entry out of
+ *           bounds has failed LAYOUT at a lower or the same index.
+ * kpref is the 32-bit key fingerprint: exporters write it, importers
+ * recompute it and ignore the stored value. Exporters write every padding
+ * byte as 0, so the same content always gives the same bytes; importers do
+ * not look at padding.
+ *
+ * THE VERDICT RULE, one for check_image, k_img_check and the tests. Header
+ * first: kImgBadHeader for fewer than 64 bytes, a wrong magic, version,
+ * header_sum, reserved word or a merge_op outside the enum; then kImgBadSize
+ * when a limit is exceeded (n_entries, payload_bytes) or len differs from
+ * image_bytes. Otherwise the failing entry with the lowest index decides; if
+ * it fails several rules the order is RECORD, LAYOUT, ORDER. kImgBadSum only
+ * when every entry passes and the records do not sum to content_sum.
+ * n_entries == 0 with payload_bytes != 0 is kImgBadSize. */
+enum : uint32_t {
+  kImgOk = 0,
+  kImgBadHeader = 1,
+  kImgBadSize = 2,
+  kImgBadRecord = 3,
+  kImgBadLayout = 4,
+  kImgBadOrder = 5,
+  kImgBadSum = 6,
+};
+constexpr size_t kImgHeaderBytes = 64;
+constexpr uint32_t kImgVersion = 1;
+constexpr uint64_t kImgMaxEntries = 1ull << 30;
+constexpr uint64_t kImgNoIndex = ~0ull;
+
+struct ImageInfo {
+  uint32_t version = 0, merge_op = 0;
+  uint64_t last_seq = 0, n_entries = 0, payload_bytes = 0, image_bytes = 0,
+           content_sum = 0;
+  uint32_t reason = kImgOk;
+  uint64_t bad_index = kImgNoIndex; /* lowest failing entry */
+};
+
+inline uint64_t img_align16(uint64_t n) { return (n + 15) & ~15ull; }
+
+/* rec_hash_cs, the record hash of gra_shard_checksum and the oracle: FNV-1a-64
+ * over (seq LE8 | type | key_len LE4 | val_len LE4 | key | value). */
+uint64_t rec_hash_host(uint64_t seq, uint8_t type, uint32_t klen, uint32_t vlen,
+                       const uint8_t *key, const uint8_t *val);
+
+/* The header half of the verdict rule: fills the header fields of *out and
+ * returns kImgOk, kImgBadHeader or kImgBadSize. Reads at most min(len, 64)
+ * bytes. */
+uint32_t check_image_header(const uint8_t *img, size_t len, ImageInfo *out);
+
+/* The whole rule over an untrusted byte string: never reads outside
+ * [img, img + len). Returns out->reason. */
+uint32_t check_image(const uint8_t *img, size_t len, ImageInfo *out);
+
+/* Serialise a run_compact result (sorted, run-relative kv_off, resident) as
+ * an image: header, headers, payload, padding zeroed, content_sum and
+ * header_sum computed. */
+void image_from_run(const Run &run, uint64_t last_seq, uint32_t merge_op,
+                    std::vector<uint8_t> *out);
+
+/* Write the 64-byte header (header_sum included) at dst. */
+void image_write_header(uint8_t *dst, uint32_t merge_op, uint64_t last_seq,
+                        uint64_t n_entries, uint64_t payload_bytes,
+                        uint64_t content_sum);
+
 /* The plan of gra_reclaim: where every live segment of the store arena goes
  * when the arena is slid down, and in which copies. Plain host code, so a CPU
  * test can hold every decision to account; the engine runs exactly this plan.

@@ -80,6 +80,35 @@ class GraCompactInfo(C.Structure):
 GRA_RECLAIM_DONE = 0
 GRA_RECLAIM_NOTHING = 1
 
+(GRA_IMG_OK, GRA_IMG_BAD_HEADER, GRA_IMG_BAD_SIZE, GRA_IMG_BAD_RECORD,
+ GRA_IMG_BAD_LAYOUT, GRA_IMG_BAD_ORDER, GRA_IMG_BAD_SUM) = range(7)
+GRA_IMG_NO_INDEX = (1 << 64) - 1
+
+
+class GraImageInfo(C.Structure):
+    _fields_ = [
+        ("version", C.c_uint32),
+        ("merge_op", C.c_uint32),
+        ("last_seq", C.c_uint64),
+        ("n_entries", C.c_uint64),
+        ("payload_bytes", C.c_uint64),
+        ("image_bytes", C.c_uint64),
+        ("content_sum", C.c_uint64),
+        ("reason", C.c_uint32),
+        ("served_by", C.c_uint32),
+        ("bad_index", C.c_uint64),
+    ]
+
+
+class ImageRejected(ValueError):
+    """GRA_CORRUPT from gra_import / gra_image_check: the image is not
+    well-formed. .info is the GraImageInfo (reason = GRA_IMG_*, bad_index =
+    the lowest failing entry or GRA_IMG_NO_INDEX)."""
+
+    def __init__(self, msg, info):
+        super().__init__(msg)
+        self.info = info
+
 
 class GraStoreUsage(C.Structure):
     _fields_ = [
@@ -218,6 +247,12 @@ def load():
     lib.gra_compact.argtypes = [C.c_void_p, C.POINTER(GraCompactInfo)]
     lib.gra_store_usage.argtypes = [C.c_void_p, C.POINTER(GraStoreUsage)]
     lib.gra_reclaim.argtypes = [C.c_void_p, C.POINTER(GraReclaimInfo)]
+    lib.gra_export.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t,
+                               C.POINTER(GraImageInfo)]
+    lib.gra_import.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t,
+                               C.POINTER(GraImageInfo)]
+    lib.gra_image_check.argtypes = [C.c_char_p, C.c_size_t,
+                                    C.POINTER(GraImageInfo)]
     lib.gra_shard_checksum.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.gra_pin_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint8))]
     lib.gra_pin_free.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
@@ -603,6 +638,52 @@ class Db:
             raise RuntimeError(f"gra_compact rc={rc}: {last_error(self.lib)}")
         return info
 
+    def export_image_raw(self, cap):
+        """One gra_export call with a buffer of cap bytes -> (rc, bytes or
+        None, info). rc is GRA_OK or GRA_BUF_TOO_SMALL (info.image_bytes is
+        then the size to come back with); everything else raises."""
+        buf = C.create_string_buffer(max(1, cap))
+        info = GraImageInfo()
+        rc = self.lib.gra_export(self.h, buf, cap, C.byref(info))
+        if rc == GRA_FULL:
+            raise StoreFullError(f"gra_export: {last_error(self.lib)}")
+        if rc not in (GRA_OK, GRA_BUF_TOO_SMALL):
+            raise RuntimeError(f"gra_export rc={rc}: {last_error(self.lib)}")
+        img = buf.raw[:info.image_bytes] if rc == GRA_OK else None
+        return rc, img, info
+
+    def export_image(self, cap=1 << 20, with_info=False):
+        """gra_export: the shard as one image (bytes) — what compact() would
+        leave of the whole shard, behind a self-checking header; the store
+        is untouched. Flushes first. Retries once, with the exact size, when
+        cap was too small. Raises StoreFullError when the arena has no
+        scratch room and RuntimeError on a store_ring engine or a shard
+        compact() could not take."""
+        rc, img, info = self.export_image_raw(cap)
+        if rc == GRA_BUF_TOO_SMALL:
+            rc, img, info = self.export_image_raw(info.image_bytes)
+        if rc != GRA_OK:
+            raise RuntimeError("gra_export: the image grew between two calls")
+        return (img, info) if with_info else img
+
+    def import_image(self, image):
+        """gra_import: install an image in this (pristine) shard; reads are
+        served from it and latest_seq() becomes its last_seq, so pulling
+        resumes behind it. Returns the GraImageInfo. Raises ImageRejected
+        (with .info) when the image is not well-formed, StoreFullError when
+        the arena cannot hold it, RuntimeError when the shard is not
+        pristine, the merge operators differ or the engine is store_ring;
+        the store is untouched in every such case."""
+        info = GraImageInfo()
+        rc = self.lib.gra_import(self.h, image, len(image), C.byref(info))
+        if rc == GRA_CORRUPT:
+            raise ImageRejected(f"gra_import: {last_error(self.lib)}", info)
+        if rc == GRA_FULL:
+            raise StoreFullError(f"gra_import: {last_error(self.lib)}")
+        if rc != GRA_OK:
+            raise RuntimeError(f"gra_import rc={rc}: {last_error(self.lib)}")
+        return info
+
     def checksum(self):
         """Order-independent full-store content checksum (device-computed;
         comparable with the oracle's orc_shard_checksum at any size)."""
@@ -644,6 +725,18 @@ class Db:
             raise RuntimeError(f"gra_get_updates rc={rc}: {last_error(self.lib)}")
         return [(out[i].seq, out[i].ts, buf.raw[out[i].off:out[i].off + out[i].len])
                 for i in range(n.value)]
+
+
+def image_check(image, lib=None):
+    """gra_image_check: the verdict rule on the host, no engine and no GPU.
+    Returns the GraImageInfo; info.reason is GRA_IMG_OK or says what is
+    wrong, info.bad_index where."""
+    lib = lib or load()
+    info = GraImageInfo()
+    rc = lib.gra_image_check(image, len(image), C.byref(info))
+    if rc not in (GRA_OK, GRA_CORRUPT):
+        raise RuntimeError(f"gra_image_check rc={rc}: {last_error(lib)}")
+    return info
 
 
 class Replay:

@@ -139,6 +139,29 @@ class Replicator:
     def reclaim_store(self):
         return self.engine.reclaim()
 
+    # ≅ AdminHandler::async_tm_backupDB (admin_handler.cpp:865-900), the
+    # data-plane half: the shard as one self-checking image (bytes); where
+    # it is kept is the caller's. Any role; the store is untouched.
+    def backup_db(self, name):
+        return self.get(name).db.export_image()
+
+    # ≅ AdminHandler::async_tm_restoreDB -> restoreDBHelper
+    # (admin_handler.cpp:902-943): register a fresh shard, install the image,
+    # then start pulling from the image's seq — the way to a replica when the
+    # upstream's retained log no longer reaches back to seq 0. The image is
+    # proven well-formed on the device before it is listed; a rejected one
+    # (ImageRejected) leaves no db registered.
+    def restore_db(self, name, image, role, upstream_db=None):
+        rs = self.add_db(name, role, upstream_db=None)  # no pull before import
+        try:
+            rs.db.import_image(image)
+        except Exception:
+            self.remove_db(name)
+            raise
+        if upstream_db is not None:
+            self.change_role(name, role, upstream_db)
+        return rs
+
     # ≅ RocksDBReplicator::write -> ReplicatedDB::Write
     # (replicated_db.cpp:103-166)
     def write(self, name, rep_bytes, mode=0):
